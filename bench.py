@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - env-steps/sec of the vectorised SkyJo hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|4] [--blocks R] [--no-other-configs]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|4] [--blocks R] [--dump-outputs DIR] [--full [--no-other-configs]]
 
 A bench "step" is ONE FUSED LAUNCH of the hot path over the whole batch: `iterations_per_step` lockstep
 iterations (1 024 at the headline size: sixteen dealing cycles of 64 in one launch of k_cycle) - in each of them
@@ -19,28 +19,35 @@ Workload (`--config 3`, the default): BASELINE.json configs[2], 65 536 parallel 
 numpy-legacy MT19937 deals (bit-identical to the reference).  `--config 4`: BASELINE.json configs[3],
 32 768 games per GPU - 262 144 in total at --gpus 8 (the shard a rank runs at N < 8 is the same size).
 
-Timing: W untimed steps, then `--blocks` (5) timed blocks of EXACTLY K steps each, every block bracketed
-by a barrier + torch.cuda.synchronize() on both sides and taken as the MAX over ranks.  `value` /
-`ms_per_step` are the MEDIAN block (env-steps counted on device over all ranks / that block's time);
-`blocks` lists every block with min / max.  Inputs are resident in HBM.  One JSON line on stdout (rank 0).
+Timing: W untimed steps, then ONE timed block of EXACTLY K steps, bracketed by a barrier +
+torch.cuda.synchronize() on both sides and taken as the MAX over ranks.  `value` is env-steps counted on device
+over all ranks / that block's time, `ms_per_step` the block's time / K.  `--blocks R` times R blocks of K steps
+each (5 under `--full`): `value` / `ms_per_step` are then the MEDIAN block, and `blocks` lists every block with
+min / max.  Inputs are resident in HBM.  One JSON line on stdout (rank 0).
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (rank 0's shard) as .npy files under DIR,
+float32 / float64, 64 MiB at most: see dump_outputs().  The games are seeded, so the same arguments give the same
+files from run to run and from build to build.
 
 `--gpus N` (N > 1) without a torchrun environment starts the N ranks itself: a fresh
 `python -m torch.distributed.run` child, started before this process touches the GPU.  With more ranks
 than GPUs the run is refused unless SKYJO_BENCH_SHARED_GPU=1 (rehearsal: ranks share cards, gloo carries
 the statistics record).
 
-Extra objects on the same line:
+A plain run does only that.  `--full` adds the measurements that take runs of their own, as extra objects on the
+same line:
   roofline       dominant kernel (k_cycle: step AND dealing wavefronts of sixteen dealing cycles) timed with HIP events
                  on its launch stream
   roofline_path  the whole path (= that one kernel in the one-kernel form; k_step + k_deal per dealing cycle in the older
                  forms): kernel-time sum from the same events, and the wall time of the timed region
-  episode_stats  what the ranks all-gather (RCCL): per-seat reward / score statistics
   other_configs  (N = 1) short blocks of the other BASELINE.json configurations in the same run: cfg2 (4 096 x 2),
                  the cfg4 shard (32 768 x 3, game_id0 = 3 * 32 768), cfg5 (65 536 x 4, the action-mask model's policy +
                  value net in the loop, float32-grade and bf16), the counter-based RNG mode (also at 131 072 games: two
                  rounds of workgroups), the direct observation
   cpu_baseline   the CPU oracle (oracle/, a port of the reference's algorithm) timed on host cores, with
-                 speedup_vs_cpu_port and speedup_vs_reference_constant beside it
+                 speedup_vs_cpu_port beside it
+  speedup_vs_reference_constant  against the reference's own loop
+Every run carries `episode_stats`: what the ranks all-gather (RCCL), per-seat reward / score statistics.
 """
 import argparse
 import json
@@ -184,6 +191,61 @@ def cpu_baseline(num_players, seconds=12.0):
     return {"value": steps / dt, "unit": "env-steps/s", "cores": threads, "kind": "port", "value_1_thread": single,
             "sample": f"{B} games x {iters} lockstep iterations ({steps} env-steps, {dt:.1f} s), "
                       f"oracle/skyjo_oracle.c with OpenMP over games, same on-device-policy restatement"}
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: all files together at most this many bytes of array data
+DUMP_SEED = 12345      # the sample of games --dump-outputs picks when a whole array would not fit
+DUMP_SEQ_GAMES = 64    # games whose records are written for every iteration of the last step
+
+
+def dump_outputs(path, eng, rec, act, planar, stats):
+    """`--dump-outputs`: what the last timed step (one fused launch of `iters` lockstep iterations) handed its caller, this rank's
+    shard, as float32 / float64 arrays in `path`/<name>.npy.  <field> runs over the record's views (vec_env.split): observations,
+    action_mask, agent, phase, done, status, episode_steps, action.
+      last_<field>     [G, ...]         the records of the step's last iteration, every game - or a seeded sample of G games where
+                                        all would take more than a third of DUMP_BYTES (last_games: their indices in the shard)
+      seq_<field>      [iters, S, ...]  the records of every iteration of the step for a seeded sample of S games (seq_games)
+      actions          [iters, S]       (--actions-array) the int32 action array of the same games
+      rewards          [G, players]     the engine's per-game rewards after the step (float64; final rewards of the last episode)
+      episode_stats    [ranks, fields]  the gathered statistics record of the last timed block (float64, distributed.stats_record)
+    Returns the total bytes written."""
+    import numpy as np
+    import torch
+
+    from skyjo_rl_amd.vec_env import Obs, split_records_np
+
+    os.makedirs(path, exist_ok=True)
+    B, D = eng.num_envs, eng.obs_dim
+    iters = rec.shape[0] if rec is not None else act.shape[0] if act is not None else 1
+    row = 4 * (D + 26 + len(Obs._fields) - 2) + 8 * (eng.num_players + 1)  # float32 record fields, float64 rewards + index of a game
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def games(n):
+        return np.arange(B) if n >= B else np.sort(rng.choice(B, n, replace=False))
+
+    last_games = games(DUMP_BYTES // 3 // row)
+    seq_games = games(max(1, min(DUMP_SEQ_GAMES, DUMP_BYTES // 3 // (iters * (row + 4)))))
+    out = {"last_games": last_games.astype(np.float64), "seq_games": seq_games.astype(np.float64)}
+    rewards = eng.rewards_tensor()
+    gl, gs = torch.as_tensor(last_games, device=rewards.device), torch.as_tensor(seq_games, device=rewards.device)
+    if rec is not None:
+        if planar:  # [iters, tiles, P, 64, 16]: the record of game 64 t + l is rec[it, t, :, l, :]
+            last = rec[-1][gl // 64, :, gl % 64, :].reshape(len(gl), -1)
+            seq = rec[:, gs // 64, :, gs % 64, :].transpose(0, 1).reshape(iters, len(gs), -1)
+        else:       # [iters, num_envs, record_bytes]
+            last, seq = rec[-1][gl], rec[:, gs]
+        for prefix, r in (("last", last), ("seq", seq)):
+            for name, v in zip(Obs._fields, split_records_np(r.cpu().numpy(), D)):
+                out[f"{prefix}_{name}"] = v.astype(np.float32)
+    if act is not None:
+        out["actions"] = act[:, gs].cpu().numpy().astype(np.float32)
+    out["rewards"] = rewards[gl].cpu().numpy().astype(np.float64)
+    out["episode_stats"] = np.asarray(stats, dtype=np.float64)
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_BYTES, f"--dump-outputs would write {total} bytes"
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    return total
 
 
 def spawn_ranks(n):
@@ -341,7 +403,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100, help="fused launches (of `iterations_per_step` lockstep iterations each) per timed block")
     ap.add_argument("--warmup", type=int, default=25, help="untimed launches before the first block")
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps launches each (value = the median block)")
+    ap.add_argument("--blocks", type=int, default=None, help="timed blocks of --steps launches each (value = the median block); "
+                                                              "default 1, 5 under --full")
+    ap.add_argument("--full", action="store_true", help="also the roofline legs, the other BASELINE configurations, the CPU baseline and "
+                                                        "the reference constants (runs of their own; a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's shard) to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--config", type=int, choices=[3, 4], default=3,
                     help="3: 65 536 games per GPU (BASELINE configs[2], weak scaling); 4: 32 768 per GPU (configs[3]: 262 144 at --gpus 8)")
     ap.add_argument("--num-envs", type=int, default=None, help="games per GPU (overrides --config)")
@@ -349,8 +416,8 @@ def main():
                     help="STRONG scaling: this many games in total, G / N per GPU (default: weak scaling, --config's games on every GPU)")
     ap.add_argument("--num-players", type=int, default=3)
     ap.add_argument("--rng", choices=["mt19937", "philox"], default="mt19937")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short blocks of the other BASELINE configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="(--full) skip the short blocks of the other BASELINE configurations")
     ap.add_argument("--no-records", action="store_true", default=bool(os.environ.get("SKYJO_BENCH_NO_RECORDS")), help="do not write records (not the headline)")
     ap.add_argument("--actions-array", action="store_true", help="also write the int32 action array (the action is byte D of every record anyway)")
     ap.add_argument("--record-layout", choices=["auto", "row-major", "tile-planar"], default=os.environ.get("SKYJO_BENCH_RECORD_LAYOUT", "auto"),
@@ -358,6 +425,8 @@ def main():
                          "wherever the kernel exists (the one-kernel form, either observation), row-major otherwise")
     ap.add_argument("--direct-obs", action="store_true", help="observe_other_player_indirect=False: D = 19 + 12 N (not the headline)")
     args = ap.parse_args()
+    if args.blocks is None:
+        args.blocks = 5 if args.full else 1
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -470,28 +539,33 @@ def main():
     steps_total = med["steps"]
     episodes = float(tot["episodes"])
 
-    # roofline leg: the same launches again, every kernel carrying a HIP event pair that receives its begin / end
-    # timestamps on its launch stream (comparable with rocprofv3's kernel trace, profiles/)
-    eng.profile(1)
-    run(32)
-    prof = eng.profile(0)
-    full = prof["step_launches"]
-    avg_ms = prof["step_ms"] / max(full, 1)
-    alg = algorithmic_bytes_per_launch(B, N, D, CHUNK, records=record) + (4 * B * CHUNK if act is not None else 0)
-    achieved = alg / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-    # NOT measured in this run: PMC counters need rocprofv3 around the process.  The figure is the committed digest of this very
-    # launch shape, and only if it was taken on the kernel sources that are built here (sha256 stored with it).
-    shape = launch_shape(B, N, CHUNK, args.rng, eng.dealing_form(), record and act is None, args.direct_obs, "tile-planar" if planar else "row-major")
-    traffic, deal_traffic, traffic_source = committed_traffic(shape)
-    path_traffic = traffic if (traffic is not None and eng.dealing_form() == "one kernel") else (
-        traffic + deal_traffic if traffic is not None and deal_traffic is not None else None)  # (k_cycle's counters already hold both roles)
-    kernel_ms = {k: prof[k + "_ms"] / 32.0 for k in ("k_step", "k_scan", "k_deal", "k_publish")}  # per bench step = per LAUNCH (k_cycle: CYCLES_PER_LAUNCH dealing cycles, slot "k_step")
-    path_ms = sum(kernel_ms.values())
     wall_ms = 1e3 * t_max / args.steps
-    # the dealing kernel's own algorithmic traffic (MT19937 mode): per RNG output one state word read as the old element, one
-    # as element i + 397, one written (12 B), plus the 24N + 150 + 16 B record, for every deal consumed in the timed region
-    deals_per_step = float(c1["resets"]) / args.steps
-    deal_alg = deals_per_step * ((24 * N + 150 + 16) + (12.0 * rng_outputs_per_deal(N) if args.rng == "mt19937" else 0.0))
+    if rank == 0 and args.dump_outputs:  # (nothing has been launched since the last timed step: the ring holds its records)
+        nbytes = dump_outputs(args.dump_outputs, eng, rec, act, planar, blocks[-1]["per_rank"])
+        sys.stderr.write(f"bench.py: {nbytes} bytes of outputs written to {args.dump_outputs}\n")
+
+    if args.full:
+        # roofline leg: the same launches again, every kernel carrying a HIP event pair that receives its begin / end
+        # timestamps on its launch stream (comparable with rocprofv3's kernel trace, profiles/)
+        eng.profile(1)
+        run(32)
+        prof = eng.profile(0)
+        full = prof["step_launches"]
+        avg_ms = prof["step_ms"] / max(full, 1)
+        alg = algorithmic_bytes_per_launch(B, N, D, CHUNK, records=record) + (4 * B * CHUNK if act is not None else 0)
+        achieved = alg / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+        # NOT measured in this run: PMC counters need rocprofv3 around the process.  The figure is the committed digest of this very
+        # launch shape, and only if it was taken on the kernel sources that are built here (sha256 stored with it).
+        shape = launch_shape(B, N, CHUNK, args.rng, eng.dealing_form(), record and act is None, args.direct_obs, "tile-planar" if planar else "row-major")
+        traffic, deal_traffic, traffic_source = committed_traffic(shape)
+        path_traffic = traffic if (traffic is not None and eng.dealing_form() == "one kernel") else (
+            traffic + deal_traffic if traffic is not None and deal_traffic is not None else None)  # (k_cycle's counters already hold both roles)
+        kernel_ms = {k: prof[k + "_ms"] / 32.0 for k in ("k_step", "k_scan", "k_deal", "k_publish")}  # per bench step = per LAUNCH (k_cycle: CYCLES_PER_LAUNCH dealing cycles, slot "k_step")
+        path_ms = sum(kernel_ms.values())
+        # the dealing kernel's own algorithmic traffic (MT19937 mode): per RNG output one state word read as the old element, one
+        # as element i + 397, one written (12 B), plus the 24N + 150 + 16 B record, for every deal consumed in the timed region
+        deals_per_step = float(c1["resets"]) / args.steps
+        deal_alg = deals_per_step * ((24 * N + 150 + 16) + (12.0 * rng_outputs_per_deal(N) if args.rng == "mt19937" else 0.0))
 
     if rank == 0:
         vals = [b["value"] for b in blocks]
@@ -547,35 +621,38 @@ def main():
                               "std_reward_per_seat": [float(x) for x in tot["std_reward"]],
                               "mean_score_per_seat": [float(x) for x in tot["mean_score"]],
                               "refunded_per_episode": float(tot["sum_refunded"].sum() / max(episodes, 1.0))},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": (f"k_cycle<{'direct' if args.direct_obs else 'indirect'},{N},{'planar' if planar else 'row-major'}> (step + dealing wavefronts of "
-                                    f"{CHUNK // max(eng.deal_interval(), 1)} dealing cycles)" if eng.dealing_form() == "one kernel" else
-                                    f"k_step<{'indirect' if not args.direct_obs else 'direct'},policy,{N if N in (2, 3, 4) else 0}>"), "avg_launch_ms": avg_ms,
-                         "launches_timed": full, "algorithmic_bytes_per_launch": alg, "launch_shape": shape,
-                         "deal_kernel_avg_ms": prof["deal_ms"] / max(prof["deal_launches"], 1)},
-            "roofline_path": {"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS,
-                              "kernel_ms_per_step": kernel_ms, "kernel_ms_sum": path_ms,
-                              "achieved_kernel_time": alg / (path_ms * 1e-3) / 1e9 if path_ms > 0 else 0.0,
-                              "frac_kernel_time": alg / (path_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if path_ms > 0 else 0.0,
-                              "wall_ms_per_step": wall_ms,
-                              "traffic": path_traffic, "traffic_k_deal_fabric": deal_traffic, "traffic_source": traffic_source,
-                              "traffic_over_algorithmic": path_traffic / alg if path_traffic is not None else None,
-                              "achieved_wall": alg / (wall_ms * 1e-3) / 1e9,
-                              "frac_wall": alg / (wall_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                              "k_deal": {"deals_per_step": deals_per_step, "rng_outputs_per_deal": rng_outputs_per_deal(N) if args.rng == "mt19937" else None,
-                                         "algorithmic_bytes_per_step": deal_alg,
-                                         "achieved": deal_alg / (kernel_ms["k_deal"] * 1e-3) / 1e9 if kernel_ms["k_deal"] > 0 else 0.0,
-                                         "frac": deal_alg / (kernel_ms["k_deal"] * 1e-3) / 1e9 / HBM_PEAK_GBS if kernel_ms["k_deal"] > 0 else 0.0},
-                              "achieved_wall_incl_dealing_bytes": (alg + deal_alg) / (wall_ms * 1e-3) / 1e9,
-                              "frac_wall_incl_dealing_bytes": (alg + deal_alg) / (wall_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                              "note": "achieved_* / frac_*: algorithmic bytes of one k_step launch (SURVEY 8d: state once + records) over the time of one "
-                                      "whole dealing cycle; *_incl_dealing_bytes adds the generator-state and record bytes the dealing kernel itself "
-                                      "has to move (not part of SURVEY 8d's per-step figure); with the dealing kernel on its own stream the kernel times "
-                                      "overlap and only the wall figures are path times"},
         }
+        if args.full:
+            out.update({
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                             "kernel": (f"k_cycle<{'direct' if args.direct_obs else 'indirect'},{N},{'planar' if planar else 'row-major'}> (step + dealing wavefronts of "
+                                        f"{CHUNK // max(eng.deal_interval(), 1)} dealing cycles)" if eng.dealing_form() == "one kernel" else
+                                        f"k_step<{'indirect' if not args.direct_obs else 'direct'},policy,{N if N in (2, 3, 4) else 0}>"), "avg_launch_ms": avg_ms,
+                             "launches_timed": full, "algorithmic_bytes_per_launch": alg, "launch_shape": shape,
+                             "deal_kernel_avg_ms": prof["deal_ms"] / max(prof["deal_launches"], 1)},
+                "roofline_path": {"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS,
+                                  "kernel_ms_per_step": kernel_ms, "kernel_ms_sum": path_ms,
+                                  "achieved_kernel_time": alg / (path_ms * 1e-3) / 1e9 if path_ms > 0 else 0.0,
+                                  "frac_kernel_time": alg / (path_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if path_ms > 0 else 0.0,
+                                  "wall_ms_per_step": wall_ms,
+                                  "traffic": path_traffic, "traffic_k_deal_fabric": deal_traffic, "traffic_source": traffic_source,
+                                  "traffic_over_algorithmic": path_traffic / alg if path_traffic is not None else None,
+                                  "achieved_wall": alg / (wall_ms * 1e-3) / 1e9,
+                                  "frac_wall": alg / (wall_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                  "k_deal": {"deals_per_step": deals_per_step, "rng_outputs_per_deal": rng_outputs_per_deal(N) if args.rng == "mt19937" else None,
+                                             "algorithmic_bytes_per_step": deal_alg,
+                                             "achieved": deal_alg / (kernel_ms["k_deal"] * 1e-3) / 1e9 if kernel_ms["k_deal"] > 0 else 0.0,
+                                             "frac": deal_alg / (kernel_ms["k_deal"] * 1e-3) / 1e9 / HBM_PEAK_GBS if kernel_ms["k_deal"] > 0 else 0.0},
+                                  "achieved_wall_incl_dealing_bytes": (alg + deal_alg) / (wall_ms * 1e-3) / 1e9,
+                                  "frac_wall_incl_dealing_bytes": (alg + deal_alg) / (wall_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                  "note": "achieved_* / frac_*: algorithmic bytes of one k_step launch (SURVEY 8d: state once + records) over the time of one "
+                                          "whole dealing cycle; *_incl_dealing_bytes adds the generator-state and record bytes the dealing kernel itself "
+                                          "has to move (not part of SURVEY 8d's per-step figure); with the dealing kernel on its own stream the kernel times "
+                                          "overlap and only the wall figures are path times"},
+            })
     eng.close()
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and not args.no_other_configs:
             out["other_configs"] = other_configs(device, max(args.steps, 10), max(args.warmup, 5))
         out["speedup_vs_reference_constant"] = {
@@ -587,6 +664,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(N)
             out["speedup_vs_cpu_port"] = {"vs_all_host_threads": med["value"] / out["cpu_baseline"]["value"],
                                           "vs_1_thread": med["value"] / out["cpu_baseline"]["value_1_thread"]}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

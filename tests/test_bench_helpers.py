@@ -68,3 +68,54 @@ def test_the_source_hash_ignores_comments_and_white_space(tmp_path, monkeypatch)
     c = bench._code_only('int f(int x) { return x + 2; }')
     assert a == b and a != c
     assert bench._code_only('const char *s = "// not a comment"; // one') == 'const char *s = "// not a comment";'
+
+
+class _HostEngine:
+    """What dump_outputs reads of an engine, on host tensors."""
+
+    def __init__(self, B, D, N):
+        import torch
+
+        self.num_envs, self.obs_dim, self.num_players = B, D, N
+        self._rewards = torch.arange(B * N, dtype=torch.float64).reshape(B, N)
+
+    def rewards_tensor(self):
+        return self._rewards.clone()
+
+
+def test_dump_outputs_reads_both_record_layouts_alike_and_keeps_to_its_budget(tmp_path, monkeypatch):
+    """--dump-outputs: the tile-planar ring [iters, tiles, P, 64, 16] and the row-major one [iters, B, record_bytes] holding the
+    same records give the same files (float32 / float64); past the byte budget the games are a seeded sample, the same every time."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    B, D, N, rb, iters = 200, 31, 3, 64, 8
+    tiles = (B + 63) // 64
+    g = torch.Generator().manual_seed(0)
+    planar = torch.randint(0, 256, (iters, tiles, rb // 16, 64, 16), dtype=torch.uint8, generator=g)
+    rows = planar.permute(0, 1, 3, 2, 4).reshape(iters, tiles * 64, rb)[:, :B].contiguous()
+    act = torch.randint(-1, 26, (iters, B), dtype=torch.int32, generator=g)
+    stats = np.arange(19.0)[None]
+    eng = _HostEngine(B, D, N)
+    bench.dump_outputs(str(tmp_path / "p"), eng, planar, act, True, stats)
+    bench.dump_outputs(str(tmp_path / "r"), eng, rows, act, False, stats)
+    names = sorted(p.name for p in (tmp_path / "p").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "r").iterdir()) and "seq_observations.npy" in names
+    for n in names:
+        a, b = np.load(tmp_path / "p" / n), np.load(tmp_path / "r" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    seq = np.load(tmp_path / "p" / "seq_games.npy").astype(int)
+    obs = np.load(tmp_path / "p" / "seq_observations.npy")
+    assert obs.shape == (iters, len(seq), D) and len(np.load(tmp_path / "p" / "last_games.npy")) == B
+    assert np.array_equal(obs[3, 5], rows[3, seq[5], :D].numpy().view(np.int8))
+    assert np.array_equal(np.load(tmp_path / "p" / "last_action.npy"), rows[-1, :, D].numpy().view(np.int8))
+    assert np.array_equal(np.load(tmp_path / "p" / "rewards.npy"), eng.rewards_tensor().numpy())
+    # a budget smaller than one iteration of every game: seeded samples, identical from call to call, within the budget
+    monkeypatch.setattr(bench, "DUMP_BYTES", 30000)
+    n1 = bench.dump_outputs(str(tmp_path / "s1"), eng, planar, act, True, stats)
+    bench.dump_outputs(str(tmp_path / "s2"), eng, planar, act, True, stats)
+    assert n1 <= 30000 and 0 < len(np.load(tmp_path / "s1" / "last_games.npy")) < B
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "s1" / n), np.load(tmp_path / "s2" / n)), n

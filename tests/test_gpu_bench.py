@@ -1,5 +1,5 @@
-"""GPU: bench.py end to end, as the driver starts it - the one-rank line with every BASELINE configuration in
-`other_configs`, and the multi-rank launch path (`--gpus 2`: bench.py spawns its own torchrun child; on this one-GPU box
+"""GPU: bench.py end to end, as the driver starts it - the plain line and its dumped outputs, the `--full` line with every
+BASELINE configuration in `other_configs`, and the multi-rank launch path (`--gpus 2`: bench.py spawns its own torchrun child; on this one-GPU box
 the two ranks share the card, which bench.py only does when told so - otherwise it refuses loudly)."""
 import json
 import os
@@ -25,7 +25,7 @@ def _line(out):
 
 
 def test_bench_line_carries_every_baseline_config():
-    d = _line(_bench("--steps", "4", "--warmup", "2", "--blocks", "3", "--no-cpu-baseline"))
+    d = _line(_bench("--full", "--steps", "4", "--warmup", "2", "--blocks", "3", "--no-cpu-baseline"))
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["unit"] == "env-steps/s" and d["value"] > 1e9
     assert d["blocks"]["n"] == 3 and d["blocks"]["min"] <= d["value"] <= d["blocks"]["max"]
     assert abs(d["value"] - d["blocks"]["median"]) < 1e-6 * d["value"]
@@ -73,10 +73,46 @@ def test_bench_two_ranks_on_one_card_rehearsal_and_refusal():
 def test_bench_flags_for_the_other_layout_and_observation():
     """`--record-layout row-major` (the ABI's default layout) and `--direct-obs` (wider records, tile-planar by default) run the same
     timed loop; the line says which layout it measured, and the PMC traffic figure is only reported for the shape it was taken on."""
-    common = ("--steps", "2", "--warmup", "1", "--blocks", "1", "--no-cpu-baseline", "--no-other-configs")
+    common = ("--full", "--steps", "2", "--warmup", "1", "--blocks", "1", "--no-cpu-baseline", "--no-other-configs")
     d = _line(_bench("--record-layout", "row-major", *common))
     assert d["config"]["record_layout"] == "row-major" and d["roofline"]["launch_shape"]["record_layout"] == "row-major"
     assert d["roofline"]["traffic"] is None and "launch shape" in d["roofline"]["traffic_source"] and d["value"] > 1e9
     d = _line(_bench("--direct-obs", *common))
     assert d["config"]["record_layout"] == "tile-planar" and d["roofline"]["launch_shape"]["direct_obs"] is True and d["value"] > 1e9
     assert "direct" in d["roofline"]["kernel"]
+
+
+def test_plain_run_times_exactly_k_steps_and_dumps_the_same_outputs_every_time(tmp_path):
+    """A plain run times ONE block of --steps launches and carries none of --full's objects; --dump-outputs writes the last timed
+    step's records (float32 / float64, 64 MiB at most), and a second run with the same arguments writes the same arrays."""
+    import numpy as np
+
+    from skyjo_rl_amd.distributed import STAT_FIELDS
+
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    lines = [_line(_bench("--steps", "3", "--warmup", "1", "--dump-outputs", str(d))) for d in dirs]
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["blocks"]["n"] == 1 and d["config"]["timed_iterations_per_block"] == 3 * d["config"]["iterations_per_step"]
+    assert abs(d["ms_per_step"] - d["blocks"]["ms_per_step"][0]) < 1e-9 and d["value"] > 1e9 and d["waits"] == 0
+    for k in ("roofline", "roofline_path", "other_configs", "cpu_baseline", "speedup_vs_reference_constant"):
+        assert k not in d, k
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == sorted(p.name for p in dirs[1].iterdir())
+    for n in ("last_observations.npy", "last_action_mask.npy", "last_action.npy", "seq_observations.npy", "rewards.npy", "episode_stats.npy"):
+        assert n in names, n
+    assert sum((dirs[0] / n).stat().st_size for n in names) <= 64 << 20
+    iters, B = d["config"]["iterations_per_step"], d["config"]["games_per_gpu"]
+    a = {n: np.load(dirs[0] / n) for n in names}
+    assert a["last_observations.npy"].shape == (B, 31) and a["seq_action_mask.npy"].shape[:2] == (iters, 64)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    # the applied action (byte D of the record) is one of the 26, or -1 where none was applied
+    assert set(np.unique(a["last_action.npy"])) <= set(range(-1, 26)) and (a["last_action.npy"] >= 0).any()
+    for n in names:
+        b = np.load(dirs[1] / n)
+        if n == "episode_stats.npy":  # counts exact; the per-seat float64 sums are accumulated by atomics (their order may differ)
+            k = len(STAT_FIELDS)
+            assert np.array_equal(a[n][:, :k], b[:, :k]) and np.allclose(a[n][:, k:], b[:, k:], rtol=1e-9, atol=0), n
+        else:
+            assert np.array_equal(a[n], b), n

@@ -54,7 +54,7 @@ def text():
     o = lambda k: oc[k]["value"]
     lines = []
     w = lines.append
-    w(f"## 6. Measurement (SURVEY §8 row d) — one MI355X, `profiles/{R}_*`, `python bench.py --steps 20 --warmup 5`")
+    w(f"## 6. Measurement (SURVEY §8 row d) — one MI355X, `profiles/{R}_*`, `python bench.py --full --steps 20 --warmup 5`")
     w("")
     w(f"(Generated from the committed profile files by `tools/design_section6.py {R}`; `tests/test_design_quotes.py` fails when a figure here")
     w("drifts from them.)  One bench step = ONE launch of `k_cycle`: " + th(iters, 0) + " lockstep iterations of all 65 536 games = sixteen dealing cycles")

@@ -11,7 +11,7 @@ for rnd in range(rounds):
         for kv in v.split():
             k, val = kv.split("=", 1)
             env["SKYJO_LIB" if k == "LIB" else k] = os.path.abspath(val) if k == "LIB" else val
-        out = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", "--no-other-configs"] + extra, env=env, capture_output=True, text=True)
+        out = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-other-configs"] + extra, env=env, capture_output=True, text=True)
         try:
             d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
         except Exception:

@@ -28,7 +28,7 @@ for w in $what; do
                 "issue SQ_WAIT_INST_ANY SQ_IFETCH SQC_ICACHE_REQ SQC_ICACHE_MISSES SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD"; do
       set -- $pass; tag=$1; shift
       rm -rf "$out/philox_$tag"
-      rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$out/philox_$tag" -- python3 "$root/bench.py" --rng philox --steps 30 --warmup 10 --blocks 1 --no-cpu-baseline --no-other-configs > "$out/philox_$tag.json" 2> "$out/philox_$tag.err"; echo "philox pmc $tag rc=$?"
+      rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$out/philox_$tag" -- python3 "$root/bench.py" --full --rng philox --steps 30 --warmup 10 --blocks 1 --no-cpu-baseline --no-other-configs > "$out/philox_$tag.json" 2> "$out/philox_$tag.err"; echo "philox pmc $tag rc=$?"
     done
   fi
 done

@@ -23,7 +23,7 @@ pids=()
 for ((r = 0; r < N; r++)); do
   RANK=$r LOCAL_RANK=$r WORLD_SIZE=$N MASTER_ADDR=127.0.0.1 MASTER_PORT=$port \
     rocprofv3 --kernel-trace --stats --output-format csv -d "$out/rank$r" -- \
-    python3 "$root/bench.py" --gpus "$N" --steps 100 --warmup 10 --blocks 3 --no-cpu-baseline --no-other-configs "$@" \
+    python3 "$root/bench.py" --full --gpus "$N" --steps 100 --warmup 10 --blocks 3 --no-cpu-baseline --no-other-configs "$@" \
     > "$out/rank$r.json" 2> "$out/rank$r.err" &
   pids+=($!)
 done
