@@ -56,6 +56,42 @@ struct DevGuard {
 
 constexpr int kMaxRolloutChunk = 128;  // lockstep iterations per k_step launch (the tile stays in LDS for a whole launch)
 constexpr int kMaxCyclesPerLaunch = 16;  // k_cycle: whole dealing cycles per launch (each of deal_every_iters iterations)
+constexpr size_t kCuLds = 160 * 1024;    // a compute unit's LDS: what a k_cycle workgroup may fill
+
+// How the dealing runs of the fused rollout are made (SKYJO_OPT_OVERLAP reports 0 for the first two, 2 for the next two, 3 for the
+// last).  resolve_form() chooses; results never depend on it.
+enum class DealForm {
+  InlineScan,             // k_deal on the caller's stream, lane = game, looks at the banks itself
+  InlineWorkList,         // k_scan + k_deal on the caller's stream (SKYJO_OPT_INLINE_WORK_LIST)
+  TwoStreamsPipelined,    // k_deal on deal_stream; the step kernel plans and publishes the runs (sk_plan_deals / sk_publish_deals)
+  TwoStreamsScanPublish,  // k_deal on deal_stream between k_scan and k_publish on the caller's stream (SKYJO_OPT_UNPIPELINED)
+  OneKernel               // k_cycle: step and dealing wavefronts in every workgroup, the pipelined protocol without a second stream
+};
+constexpr bool uses_deal_stream(DealForm f) { return f == DealForm::TwoStreamsPipelined || f == DealForm::TwoStreamsScanPublish; }
+
+// What the caller asked for, as it asked (skyjo_vec_set_option); resolve_form() turns it into a DealForm.
+struct DealRequests {
+  int overlap = -1;  // SKYJO_OPT_OVERLAP 0 .. 3, -1: never set (the engine's own choice)
+  bool unpipelined = false, inline_work_list = false;
+  bool no_bank = false;  // SKYJO_OPT_NO_BANK: no pre-dealt episodes, every deal is made in place from the stream's position
+  int cycle_s = 0;   // SKYJO_OPT_CYCLE_S (0: the batch's share)
+};
+
+// The dealing run that has been started and not yet published.
+enum class InFlight {
+  None,
+  ListRun,  // a work-list run on deal_stream: k_publish makes its episodes available
+  Planned,  // a run the step kernel planned, waiting for the k_cycle launch that carries it (inflight_tag: its id)
+  Dealing   // a planned run that is being dealt or has been: the next step kernel publishes it, or k_publish_all
+};
+
+// k_deal's third argument: where the run's games come from and who publishes its episodes
+enum class DealRun : int {
+  ListBeside = 0,  // the work list; k_publish follows
+  ListInline = 1,  // the work list; k_deal publishes
+  ScanInline = 2,  // lane = game, own scan; k_deal publishes
+  Planned = 3      // lane = game, planned by the step kernel, which also publishes
+};
 // Default number of lockstep iterations between two dealing runs.  A run adds one episode to every bank that is not
 // full, so the interval has to stay below the mean episode length of the policy in use (random admissible policy:
 // 76 / 105 / 134 steps for 2 / 3 / 4 players) or the banks of SK_BANK episodes drain and finished games deal in
@@ -67,15 +103,20 @@ constexpr int kMaxCyclesPerLaunch = 16;  // k_cycle: whole dealing cycles per la
 // caller's stream waits for every run; 80 / 56 in the pipelined form (the default), where a step launch should outlast
 // the dealing kernel beside it (32 768 x 3 players: 64 -> 17.5, 72 -> 19.0, 80 -> 19.4, 88 -> 19.9 x 10^9 steps/s with one
 // bank run dry; 4 096 x 2 players: 48 -> 2.3, 56 -> 2.7, 64 -> 2.9 x 10^9 with twelve).
-// The one-kernel form (k_cycle, merged_s = its S): on a full chip (S = 4, a step and a dealing wavefront on every SIMD) a launch
+// The one-kernel form (k_cycle, cycle_s = its S): on a full chip (S = 4, a step and a dealing wavefront on every SIMD) a launch
 // should last about as long as its dealing wavefronts - 65 536 x 3 players: 48 -> 32.7, 56 -> 36.0, 60 -> 37.1, 64 -> 37.3, 68 ->
 // 36.8, 72 -> 36.5, 80 -> 35.7 x 10^9 steps/s; two players: 40 -> 28.3, 48 -> 30.3, 56 -> 31.3 (64 empties banks).  With S < 4 every
 // wavefront has a SIMD to itself, the dealing is hidden anyway and longer launches win (32 768 x 3: 56 -> 22.4, 72 -> 23.2, 80 -> 23.4;
 // 32 768 x 4: 64 -> 22.6, 80 -> 23.1, 96 -> 23.7, 112 -> 24.0; 4 096 x 2: 40 -> 2.44, 48 -> 2.88, 56 -> 2.98).
-constexpr int deal_interval_default(int num_players, bool overlap, bool piped, int merged_s = 0) {
-  if (merged_s >= 4) return num_players >= 3 ? 64 : 56;
-  if (merged_s > 0) return num_players >= 4 ? 104 : (num_players == 3 ? 80 : 56);
-  return overlap ? (piped ? (num_players >= 3 ? 80 : 56) : (num_players >= 3 ? 64 : 48)) : (num_players >= 3 ? 88 : 64);
+constexpr int deal_interval_default(int num_players, DealForm form, int cycle_s) {
+  switch (form) {
+    case DealForm::OneKernel:
+      if (cycle_s >= 4) return num_players >= 3 ? 64 : 56;
+      return num_players >= 4 ? 104 : (num_players == 3 ? 80 : 56);
+    case DealForm::TwoStreamsPipelined: return num_players >= 3 ? 80 : 56;
+    case DealForm::TwoStreamsScanPublish: return num_players >= 3 ? 64 : 48;
+    default: return num_players >= 3 ? 88 : 64;
+  }
 }
 
 }  // namespace
@@ -95,7 +136,7 @@ struct skyjo_vec {
   size_t lds_rollout = 0, lds_step = 0;  // the step kernels of 2 / 3 / 4 players keep their statistics in registers: smaller footprints (fused rollout / caller actions)
   bool seeded = false;
   int pending_iters = 0;  // lockstep iterations since the dealing kernel last ran
-  int deal_every_iters = 64;  // set from deal_interval_default() in skyjo_vec_create
+  int deal_every_iters = 64;  // (resolve_form sets it with interval_default)
   // The interval adapts itself unless it was set explicitly: every dealing run reports how many banks it found empty
   // (host-mapped word, no synchronisation); any empty bank shortens the interval, a long calm stretch lengthens it
   // back towards the default.  Results never depend on the cadence (tests/test_gpu_parity.py), only the speed does.
@@ -103,23 +144,17 @@ struct skyjo_vec {
   int interval_default = 64, calm_runs = 0;
   uint32_t health_seen = 0;
   uint32_t *health_host = nullptr;
-  // dealing pipeline: k_scan / k_publish on the caller's stream, k_deal on deal_stream when overlap is on
-  bool overlap = true;
-  bool fused_scan = true;  // in line: k_deal looks at the banks itself (SKYJO_FUSED_SCAN=0: diagnostic, the k_scan + work list form)
-  hipStream_t deal_stream = nullptr;
+  // the dealing form: requests -> resolve_form() -> form and, for k_cycle, its workgroup shape
+  DealRequests req;
+  DealForm form = DealForm::InlineScan;
+  bool one_kernel_capable = false;  // two to four players and k_cycle may use a whole CU's LDS
+  int cycle_s = SK_CYCLE_MAX_S;     // step (= dealing) wavefronts per workgroup of k_cycle
+  size_t lds_cycle = 0, lds_cycle_step = 0;  // k_cycle's dynamic LDS and one step wavefront's region in it, for the record layout in force
+  uint32_t cycle_deal_arg = 0;      // k_cycle's lds_deal_bytes argument: a dealing wavefront's region | the flag bits (skyjo_cycle.h)
+  hipStream_t deal_stream = nullptr;  // k_deal's stream in the two-stream forms
   hipEvent_t ev_scan = nullptr, ev_dealt = nullptr;
-  bool deal_inflight = false;
-  bool piped = true;           // beside the step kernel: the step kernel plans / publishes the runs itself (SKYJO_PIPELINED=0: k_scan + k_publish)
-  // Full-chip batches of two / three players (indirect observation): ONE kernel per dealing cycle, k_cycle - eight wavefronts per
-  // CU, the four on SIMDs 0 / 2 step, the four on SIMDs 1 / 3 deal the run the previous launch planned (the pipelined protocol,
-  // no second stream).  cycle_deal_tag != 0: a planned run waits for the next launch to carry it.
-  bool merged = false, merged_capable = false, prefer_merged = false;
-  uint32_t cycle_deal_tag = 0;
-  size_t lds_cycle = 0;
-  int cycle_s = SK_CYCLE_MAX_S;  // step (= dealing) wavefronts per workgroup of k_cycle
-  size_t lds_cycle_step = 0;     // one step wavefront's LDS region in k_cycle (lds_rollout, or lds_step when the deferred scoring has no room)
-  bool cycle_no_defer = false;
-  bool inflight_piped = false; // the run(s) in flight were planned that way
+  InFlight inflight = InFlight::None;
+  uint32_t inflight_tag = 0;
   int list_sel = 0;
   uint32_t deal_tag = 0;  // k_step launches between two k_deal launches inside skyjo_vec_rollout
   uint64_t iter = 0;        // rollout iterations (the policy's Philox counter)
@@ -143,7 +178,6 @@ struct skyjo_vec {
   int max_cycles = 0;       // SKYJO_OPT_MAX_CYCLES_PER_LAUNCH (0: the ABI's maximum, kMaxCyclesPerLaunch)
   bool rec_planar_all = false;  // ... = SKYJO_REC_TILE_PLANAR_ALL: reset / observe / step / step_collect / model_rollout write their records tile-planar as well
   bool rec_planar = false;  // SKYJO_OPT_RECORD_LAYOUT: skyjo_vec_rollout writes its records tile-planar (one-kernel form, either observation)
-  bool no_bank = false;  // SKYJO_OPT_NO_BANK: no pre-dealt episodes, every deal is made in place from the stream's position
   // lazily allocated scratch for the *_host conveniences
   int32_t *d_actions = nullptr;
   uint8_t *d_records = nullptr;
@@ -230,56 +264,85 @@ int prof_events(skyjo_vec *h, int kernel, hipEvent_t *a, hipEvent_t *b) {
   return SKYJO_OK;
 }
 
-// Make the episodes of the dealing launch that may still be running available (k_publish on the caller's stream).
-static int launch_deal_kernel(skyjo_vec *h, hipStream_t ds, int mode, int be_read = -1);
-// k_cycle form: a run that was planned but whose carrying launch never came (the caller went on with another kind of call) is
-// dealt here, by the dealing kernel alone on the caller's stream.
-int flush_cycle_deal(skyjo_vec *h, hipStream_t s) {
-  if (!h->cycle_deal_tag) return SKYJO_OK;
+// ---- one table per kernel family: the instantiations that exist, and the only places that name them (the order of the rows is the
+// order of the kernels in the code object, nothing else) ----
+constexpr uint32_t kDealLds = SK_TILE * (SK_DECK_STRIDE + SK_STG_STRIDE);  // a dealing wavefront of two to four players: byte decks + MtChunkStream's staging rows
+constexpr int fixed_players(int n) { return n >= 2 && n <= 4 ? n : 0; }    // the player counts with kernels of their own; 0: the generic ones
+
+template <class Fn>
+struct KernelRow {
+  int key;  // kernel_key() of the template arguments
+  Fn fn;
+};
+constexpr int kernel_key(int players, bool indirect = false, bool planar = false, bool policy = false) {
+  return players | indirect << 4 | planar << 5 | policy << 6;
+}
+template <class Fn, size_t K>
+Fn find_kernel(const KernelRow<Fn> (&table)[K], int key) {
+  for (const KernelRow<Fn> &r : table)
+    if (r.key == key) return r.fn;
+  return nullptr;
+}
+
+constexpr KernelRow<decltype(&k_deal<2>)> kDealKernels[] = {{2, k_deal<2>}, {3, k_deal<3>}, {4, k_deal<4>}, {0, k_deal<0>}};
+
+// PL: the records leave tile-planar (SKYJO_OPT_RECORD_LAYOUT)
+#define SK_ROW(I, NP, PL) {kernel_key(NP, I, PL), k_cycle<I, NP, PL>}
+#define SK_ROWS(I, PL) SK_ROW(I, 2, PL), SK_ROW(I, 3, PL), SK_ROW(I, 4, PL)
+constexpr KernelRow<decltype(&k_cycle<true, 2, false>)> kCycleKernels[] = {SK_ROWS(true, false), SK_ROWS(true, true), SK_ROWS(false, true), SK_ROWS(false, false)};
+#undef SK_ROWS
+#undef SK_ROW
+
+// PL: caller actions, indirect observation, two to four players only (SKYJO_REC_TILE_PLANAR_ALL checks that when it is set)
+#define SK_ROW(I, Pol, NP, PL) {kernel_key(NP, I, PL, Pol), k_step<I, Pol, NP, PL>}
+#define SK_ROWS(I, Pol) SK_ROW(I, Pol, 2, false), SK_ROW(I, Pol, 3, false), SK_ROW(I, Pol, 4, false), SK_ROW(I, Pol, 0, false)
+constexpr KernelRow<decltype(&k_step<true, true, 2>)> kStepKernels[] = {SK_ROW(true, false, 2, true), SK_ROW(true, false, 3, true), SK_ROW(true, false, 4, true),
+                                                                        SK_ROWS(true, true), SK_ROWS(true, false), SK_ROWS(false, true), SK_ROWS(false, false)};
+#undef SK_ROWS
+#undef SK_ROW
+
+// `be_read`: the bank_empty word the run reports (default: the run's own parity, as the step kernel that planned it counted)
+int launch_deal_kernel(skyjo_vec *h, hipStream_t ds, DealRun run, int be_read = -1) {
+  hipEvent_t e0, e1;
+  int rc;
+  h->P.be_read = be_read >= 0 ? (uint32_t)be_read : (h->P.deal_tag & 1u);
+  if ((rc = prof_events(h, 2, &e0, &e1))) return rc;
+  const int np = fixed_players(h->P.L.N);
+  // fixed player counts deal from a byte deck per lane; the generic kernel needs the tile + ring
+  hipExtLaunchKernelGGL(find_kernel(kDealKernels, kernel_key(np)), dim3(h->P.tiles), dim3(SK_TILE), np ? kDealLds : (uint32_t)(h->lds_tile + 16384), ds, e0, e1, 0, h->P,
+                        h->list_sel, (int)run);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+// Planned -> Dealing without the k_cycle launch that should have carried the run (the caller went on with another kind of call):
+// the dealing kernel alone, on the caller's stream.
+int flush_planned(skyjo_vec *h, hipStream_t s) {
+  if (h->inflight != InFlight::Planned) return SKYJO_OK;
   const uint32_t keep = h->P.deal_tag;
-  h->P.deal_tag = h->cycle_deal_tag;
-  h->cycle_deal_tag = 0;
-  const int rc = launch_deal_kernel(h, s, 3, (int)((h->cycle_seq - 1u) & 1u));  // (the word the k_cycle launch that planned it counted into)
+  h->P.deal_tag = h->inflight_tag;
+  h->inflight = InFlight::Dealing;
+  const int rc = launch_deal_kernel(h, s, DealRun::Planned, (int)((h->cycle_seq - 1u) & 1u));  // (the word the k_cycle launch that planned it counted into)
   h->P.deal_tag = keep;
   return rc;
 }
 
+// Any state -> None: the episodes of the run in flight become available on stream `s`.
 int publish_deals(skyjo_vec *h, hipStream_t s) {
-  int rcf = flush_cycle_deal(h, s);
-  if (rcf) return rcf;
-  if (!h->deal_inflight) return SKYJO_OK;
-  if (h->overlap && !h->merged) HIPCHK(hipStreamWaitEvent(s, h->ev_dealt, 0));
-  hipEvent_t e0, e1;
-  int rc = prof_events(h, 3, &e0, &e1);
+  int rc = flush_planned(h, s);
   if (rc) return rc;
-  if (h->inflight_piped) {
+  if (h->inflight == InFlight::None) return SKYJO_OK;
+  if (uses_deal_stream(h->form)) HIPCHK(hipStreamWaitEvent(s, h->ev_dealt, 0));
+  hipEvent_t e0, e1;
+  if ((rc = prof_events(h, 3, &e0, &e1))) return rc;
+  if (h->inflight == InFlight::ListRun) {
+    hipExtLaunchKernelGGL(k_publish, dim3(64), dim3(256), 0, s, e0, e1, 0, h->P, h->list_sel);
+  } else {
     const int G = h->P.tiles * SK_TILE;
     hipExtLaunchKernelGGL(k_publish_all, dim3((G + 255) / 256), dim3(256), 0, s, e0, e1, 0, h->P);
-  } else {
-    hipExtLaunchKernelGGL(k_publish, dim3(64), dim3(256), 0, s, e0, e1, 0, h->P, h->list_sel);
   }
   HIPCHK(hipGetLastError());
-  h->deal_inflight = false, h->inflight_piped = false;
-  return SKYJO_OK;
-}
-
-// mode: 0 = work list, beside the step kernel (k_publish follows); 1 = work list, in line; 2 = in line, lane = game, own
-// scan; 3 = beside the step kernel, lane = game, planned by the step kernel (sk_plan_deals)
-int launch_deal_kernel(skyjo_vec *h, hipStream_t ds, int mode, int be_read) {
-  hipEvent_t e0, e1;
-  int rc;
-  h->P.be_read = be_read >= 0 ? (uint32_t)be_read : (h->P.deal_tag & 1u);  // (two-stream form: the run's own parity, as the step kernel that planned it counted)
-  if ((rc = prof_events(h, 2, &e0, &e1))) return rc;
-  // fixed player counts deal from a byte deck per lane; the generic kernel needs the tile + ring
-  const uint32_t lds_compact = SK_TILE * (SK_DECK_STRIDE + SK_STG_STRIDE),  // decks + MtChunkStream's staging rows
-                  lds_generic = (uint32_t)(h->lds_tile + 16384);
-  switch (h->P.L.N) {
-    case 2: hipExtLaunchKernelGGL(k_deal<2>, dim3(h->P.tiles), dim3(SK_TILE), lds_compact, ds, e0, e1, 0, h->P, h->list_sel, mode); break;
-    case 3: hipExtLaunchKernelGGL(k_deal<3>, dim3(h->P.tiles), dim3(SK_TILE), lds_compact, ds, e0, e1, 0, h->P, h->list_sel, mode); break;
-    case 4: hipExtLaunchKernelGGL(k_deal<4>, dim3(h->P.tiles), dim3(SK_TILE), lds_compact, ds, e0, e1, 0, h->P, h->list_sel, mode); break;
-    default: hipExtLaunchKernelGGL(k_deal<0>, dim3(h->P.tiles), dim3(SK_TILE), lds_generic, ds, e0, e1, 0, h->P, h->list_sel, mode); break;
-  }
-  HIPCHK(hipGetLastError());
+  h->inflight = InFlight::None;
   return SKYJO_OK;
 }
 
@@ -312,154 +375,98 @@ static void next_deal_tag(skyjo_vec *h, bool flip_list) {
   h->P.deal_tag = h->deal_tag;
 }
 
-// One dealing cycle: publish the previous one, list the banks that are not full, deal one episode for each.
-// With overlap on, k_deal runs on its own stream beside the k_step launches that follow; its episodes are
-// published at the start of the next cycle (one dealing interval later), long before a bank of SK_BANK runs dry.
+// One dealing run that the step kernel did not plan: publish the previous one, then deal one episode for every bank that is not
+// full.  In line (-> None) k_deal publishes its own episodes; in the two-stream forms (-> ListRun) it runs on deal_stream beside the
+// step launches that follow, and its episodes are published at the start of the next run, long before a bank of SK_BANK runs dry.
+// The forms that do not plan make every run this way; seeding and resets fill the banks this way in every form.
 int start_deals(skyjo_vec *h, hipStream_t s) {
   int rc;
-  if (h->no_bank) {  // nothing is ever dealt ahead: a reset deals in place (deal_inline)
+  if (h->req.no_bank) {  // nothing is ever dealt ahead: a reset deals in place (deal_inline)
     h->pending_iters = 0;
     return SKYJO_OK;
   }
   if ((rc = publish_deals(h, s))) return rc;
   adapt_interval(h);
   next_deal_tag(h, true);
-  // (the list's counter was cleared by the previous run's publish step)
-  hipEvent_t e0, e1;
-  // In line, the dealing kernel looks at the banks itself (lane = game): no k_scan launch, no work list.  Beside the step
-  // kernel the list is made here, on the caller's stream, where it is ordered with the step launches around it.
-  const bool fused = !h->overlap && h->fused_scan;
-  if (!fused) {
+  // In line, the dealing kernel looks at the banks itself (lane = game) unless the work list was asked for: no k_scan launch.  Beside
+  // the step kernel the list is made here, on the caller's stream, where it is ordered with the step launches around it (its counter
+  // was cleared by the previous run's publish step).
+  const bool beside = uses_deal_stream(h->form);
+  const DealRun run = beside ? DealRun::ListBeside : h->req.inline_work_list ? DealRun::ListInline : DealRun::ScanInline;
+  if (run != DealRun::ScanInline) {
+    hipEvent_t e0, e1;
     if ((rc = prof_events(h, 1, &e0, &e1))) return rc;
     hipExtLaunchKernelGGL(k_scan, dim3((h->P.B + SK_SCAN_BLOCK - 1) / SK_SCAN_BLOCK), dim3(SK_SCAN_BLOCK), 0, s, e0, e1, 0, h->P,
                           h->list_sel);
     HIPCHK(hipGetLastError());
   }
-  hipStream_t ds = s;
-  if (h->overlap) {
+  if (beside) {
     HIPCHK(hipEventRecord(h->ev_scan, s));
     HIPCHK(hipStreamWaitEvent(h->deal_stream, h->ev_scan, 0));
-    ds = h->deal_stream;
   }
-  const int inl = h->overlap ? 0 : (fused ? 2 : 1);  // in line: k_deal publishes its own episodes, no k_publish launch
-  if ((rc = launch_deal_kernel(h, ds, inl))) return rc;
-  if (h->overlap) HIPCHK(hipEventRecord(h->ev_dealt, ds));
-  h->deal_inflight = h->overlap;
+  if ((rc = launch_deal_kernel(h, beside ? h->deal_stream : s, run))) return rc;
+  if (beside) {
+    HIPCHK(hipEventRecord(h->ev_dealt, h->deal_stream));
+    h->inflight = InFlight::ListRun;
+  }
   h->pending_iters = 0;
   return SKYJO_OK;
 }
 
-// The pipelined form of a dealing cycle beside the step kernel (skyjo_device.h, sk_plan_deals): plan_cycle() before the
-// step launch after which the run is due - that launch plans the run on its way out -, start_deals_piped() after it:
-// the dealing kernel goes to its own stream behind an event for that launch.  Nothing on the caller's stream waits.
-static bool piped_mode(const skyjo_vec *h) { return ((h->overlap && h->piped) || h->merged) && !h->no_bank; }
-static void plan_cycle(skyjo_vec *h) {
+// The pipelined protocol (skyjo_device.h, sk_plan_deals) of TwoStreamsPipelined and OneKernel: plan_cycle() before the step launch
+// after which the run is due - that launch plans the run on its way out -, start_deals_planned() after it.  Nothing on the caller's
+// stream waits.
+bool plans_ahead(const skyjo_vec *h) {
+  return (h->form == DealForm::TwoStreamsPipelined || h->form == DealForm::OneKernel) && !h->req.no_bank;
+}
+void plan_cycle(skyjo_vec *h) {
   next_deal_tag(h, false);
   h->P.plan_new_tag = h->deal_tag;
   h->P.be_add = h->deal_tag & 1u;  // (a k_cycle launch overrides this with its launch parity: launch_step)
   h->P.ov_flags |= 2u;
 }
-int start_deals_piped(skyjo_vec *h, hipStream_t s) {
+int start_deals_planned(skyjo_vec *h, hipStream_t s) {
   int rc;
-  if (h->merged) {  // the next k_cycle launch carries the run (its wavefronts on SIMDs 1 / 3); nothing is launched here
-    if ((rc = flush_cycle_deal(h, s))) return rc;  // (an older run that no launch has carried yet: deal it now)
-    h->cycle_deal_tag = h->deal_tag;
-    h->deal_inflight = true, h->inflight_piped = true;
-    h->pending_iters = 0;
-    adapt_interval(h);
-    return SKYJO_OK;
+  if (h->form == DealForm::OneKernel) {  // -> Planned: the next k_cycle launch carries the run; nothing is launched here
+    if ((rc = flush_planned(h, s))) return rc;  // (an older run that no launch has carried yet: deal it now)
+    h->inflight = InFlight::Planned, h->inflight_tag = h->deal_tag;
+  } else {  // -> Dealing: the dealing kernel goes to its own stream behind an event for the launch that planned the run
+    HIPCHK(hipEventRecord(h->ev_scan, s));
+    HIPCHK(hipStreamWaitEvent(h->deal_stream, h->ev_scan, 0));
+    if ((rc = launch_deal_kernel(h, h->deal_stream, DealRun::Planned))) return rc;
+    HIPCHK(hipEventRecord(h->ev_dealt, h->deal_stream));
+    h->inflight = InFlight::Dealing;
   }
-  HIPCHK(hipEventRecord(h->ev_scan, s));
-  HIPCHK(hipStreamWaitEvent(h->deal_stream, h->ev_scan, 0));
-  if ((rc = launch_deal_kernel(h, h->deal_stream, 3))) return rc;
-  HIPCHK(hipEventRecord(h->ev_dealt, h->deal_stream));
-  h->deal_inflight = true, h->inflight_piped = true;
   h->pending_iters = 0;
   adapt_interval(h);  // (for the cycles to come)
   return SKYJO_OK;
 }
+// the run that is due after a step launch, in the engine's form
+int start_due_deals(skyjo_vec *h, hipStream_t s) { return plans_ahead(h) ? start_deals_planned(h, s) : start_deals(h, s); }
 
 int launch_step(skyjo_vec *h, hipStream_t s, bool policy, const int32_t *actions, uint8_t *rec, int32_t *act_out,
                 int iters, uint64_t policy_seed, double *end_rew = nullptr, uint8_t *end_flag = nullptr, uint8_t *raw_out = nullptr,
                 int cycle_len = 0, bool planar_out = false) {
   h->raw_valid = false;  // (the host's copy of the games is stale from here on; step_host sets it again)
-  dim3 grid(h->P.tiles), block(SK_TILE);
   const bool ind = h->P.L.indirect != 0;
   int rc;
   hipEvent_t e0, e1;
   if ((rc = prof_events(h, 0, &e0, &e1))) return rc;
-  if (h->deal_inflight && h->inflight_piped) h->P.ov_flags |= 1u;  // publish what has been dealt since (sk_publish_deals)
-  if (h->merged && policy && !end_rew && !raw_out) {
-    // one kernel for the whole dealing cycle: S step + S dealing wavefronts per workgroup (= per CU)
-    uint32_t lds_deal = SK_TILE * (SK_DECK_STRIDE + SK_STG_STRIDE), tag = h->cycle_deal_tag;
-    h->cycle_deal_tag = 0;
-    size_t lds_step_region = h->lds_cycle_step, lds_total = h->lds_cycle;
-    bool no_defer = h->cycle_no_defer;
-    if (h->rec_planar && !ind) {
-      // the direct observation's wide records leave from registers in this layout: the staging area shrinks to the rare paths' 4 KiB of
-      // scratch, and where the card chunks of the deferred scoring did not fit beside it (three players on a full chip) they do now
-      const size_t base = h->lds_tile + 4096, with_defer = base + (size_t)h->P.L.N * 1024;
-      no_defer = (size_t)h->cycle_s * (with_defer + lds_deal) + 32 > 160 * 1024;
-      lds_step_region = no_defer ? base : with_defer;
-      lds_total = (size_t)h->cycle_s * (lds_step_region + lds_deal) + 32;
-    }
-    if (no_defer) lds_deal |= 1u << 29;
-    if (const char *e = sk_diag_env("SKYJO_CYCLE_SPLIT")) lds_deal |= (uint32_t)(atoi(e) & 3) << 30;  // diagnostic: 1 = roles by SIMD parity, 2 = by SIMD pair
+  if (h->inflight == InFlight::Planned || h->inflight == InFlight::Dealing) h->P.ov_flags |= 1u;  // publish what has been dealt since (sk_publish_deals)
+  if (h->form == DealForm::OneKernel && policy && !end_rew && !raw_out) {
+    // one kernel for the whole dealing cycle: S step + S dealing wavefronts per workgroup (= per CU); Planned -> Dealing
+    uint32_t tag = 0;
+    if (h->inflight == InFlight::Planned) tag = h->inflight_tag, h->inflight = InFlight::Dealing;
     h->P.be_add = h->cycle_seq & 1u, h->P.be_read = (h->cycle_seq & 1u) ^ 1u;
     h->cycle_seq++;
     const int S = h->cycle_s;
-    dim3 cgrid((h->P.tiles + S - 1) / S), cblock(2 * S * SK_TILE);
-#define LAUNCHC(I, NP, PL)                                                                                                                 \
-  hipExtLaunchKernelGGL((k_cycle<I, NP, PL>), cgrid, cblock, (uint32_t)lds_total, s, e0, e1, 0, h->P, rec, act_out, iters, policy_seed, \
-                        h->iter, tag, (uint32_t)lds_step_region, lds_deal, cycle_len)
-    switch (h->P.L.N * 2 + (ind ? 1 : 0) + (h->rec_planar ? 100 : 0)) {
-      case 5: LAUNCHC(true, 2, false); break;
-      case 7: LAUNCHC(true, 3, false); break;
-      case 9: LAUNCHC(true, 4, false); break;
-      case 105: LAUNCHC(true, 2, true); break;
-      case 107: LAUNCHC(true, 3, true); break;
-      case 109: LAUNCHC(true, 4, true); break;
-      case 104: LAUNCHC(false, 2, true); break;
-      case 106: LAUNCHC(false, 3, true); break;
-      case 108: LAUNCHC(false, 4, true); break;
-      case 4: LAUNCHC(false, 2, false); break;
-      case 6: LAUNCHC(false, 3, false); break;
-      default: LAUNCHC(false, 4, false); break;
-    }
-#undef LAUNCHC
-    HIPCHK(hipGetLastError());
-    h->P.ov_flags = 0;
-    h->iters_total += (uint64_t)iters;
-    h->iter += (uint64_t)iters;
-    h->pending_iters += iters;
-    return SKYJO_OK;
+    hipExtLaunchKernelGGL(find_kernel(kCycleKernels, kernel_key(h->P.L.N, ind, h->rec_planar)), dim3((h->P.tiles + S - 1) / S), dim3(2 * S * SK_TILE), (uint32_t)h->lds_cycle, s,
+                          e0, e1, 0, h->P, rec, act_out, iters, policy_seed, h->iter, tag, (uint32_t)h->lds_cycle_step, h->cycle_deal_arg, cycle_len);
+  } else {
+    if ((rc = flush_planned(h, s))) return rc;  // (another kind of step: a planned run does not wait for a k_cycle launch)
+    hipExtLaunchKernelGGL(find_kernel(kStepKernels, kernel_key(fixed_players(h->P.L.N), ind, ind && !policy && planar_out, policy)), dim3(h->P.tiles), dim3(SK_TILE), (uint32_t)(policy ? h->lds_rollout : h->lds_step), s, e0, e1, 0, h->P, actions, rec, act_out,
+                          iters, policy_seed, h->iter, end_rew, end_flag, raw_out, h->raw_stride);
   }
-  if ((rc = flush_cycle_deal(h, s))) return rc;  // (another kind of step: a planned run does not wait for a k_cycle launch)
-#define LAUNCH3(I, Pol, NP)                                                                                       \
-  hipExtLaunchKernelGGL((k_step<I, Pol, NP>), grid, block, (uint32_t)(Pol ? h->lds_rollout : h->lds_step), s, e0, e1, 0, h->P, actions,   \
-                        rec, act_out, iters, policy_seed, h->iter, end_rew, end_flag, raw_out, h->raw_stride)
-#define LAUNCH(I, Pol)                                \
-  switch (h->P.L.N) {                                 \
-    case 2: LAUNCH3(I, Pol, 2); break;                \
-    case 3: LAUNCH3(I, Pol, 3); break;                \
-    case 4: LAUNCH3(I, Pol, 4); break;                \
-    default: LAUNCH3(I, Pol, 0); break;               \
-  }
-  if (ind && !policy && planar_out) {  // (SKYJO_REC_TILE_PLANAR_ALL: two to four players, indirect observation - checked when the option is set)
-#define LAUNCHP(NP) hipExtLaunchKernelGGL((k_step<true, false, NP, true>), grid, block, (uint32_t)h->lds_step, s, e0, e1, 0, h->P, actions, rec, act_out, iters, \
-                                          policy_seed, h->iter, end_rew, end_flag, raw_out, h->raw_stride)
-    switch (h->P.L.N) {
-      case 2: LAUNCHP(2); break;
-      case 3: LAUNCHP(3); break;
-      default: LAUNCHP(4); break;
-    }
-#undef LAUNCHP
-  } else if (ind && policy) LAUNCH(true, true)
-  else if (ind) LAUNCH(true, false)
-  else if (policy) LAUNCH(false, true)
-  else LAUNCH(false, false)
-#undef LAUNCH3
-#undef LAUNCH
   HIPCHK(hipGetLastError());
   h->P.ov_flags = 0;
   h->iters_total += (uint64_t)iters;
@@ -493,57 +500,91 @@ int launch_mlp(const skyjo_vec_mlp *ma, const skyjo_vec_mlp *mb, int nets, const
   return SKYJO_OK;
 }
 
-// (Re)sizes the one-kernel form for this engine: called by skyjo_vec_create and by SKYJO_OPT_CYCLE_S.
-static void configure_cycle(skyjo_vec *h, int s_override) {
-  // k_cycle: S step + S dealing wavefronts per workgroup, S = what spreads the batch over the 256 CUs (1 .. 4); their LDS
-    // regions and the claim words must fit one CU's 160 KB
-    const int ncu = h->ncu;
-    const SkParams &P = h->P;
-    const bool fixed_n = P.L.N >= 2 && P.L.N <= 4;
-    int S = (P.tiles + ncu - 1) / ncu;
-    S = S < 1 ? 1 : (S > SK_CYCLE_MAX_S ? SK_CYCLE_MAX_S : S);
-    if (s_override >= 1 && s_override <= SK_CYCLE_MAX_S) S = s_override;  // (SKYJO_OPT_CYCLE_S: fewer / more wavefronts per workgroup than the batch's share)
-    const int natural_s = S;
-    const size_t deal_region = (size_t)SK_TILE * (SK_DECK_STRIDE + SK_STG_STRIDE);
-    size_t per_s = h->lds_rollout + deal_region;
-    h->lds_cycle_step = h->lds_rollout, h->cycle_no_defer = false;
-    if ((size_t)S * per_s + 32 > 160 * 1024 && (size_t)S * (h->lds_step + deal_region) + 32 <= 160 * 1024 && P.L.N <= 3 &&
-        !sk_diag_env("SKYJO_CYCLE_DEFER_ONLY")) {
-      // the direct observation of three players on a full chip: the CU's share of tiles fits without the card chunks of the deferred
-      // scoring (the games are then scored in the iteration they end: a slower step, but one round of workgroups - 31.0 against 23.5
-      // x 10^9 in line; four players, where scoring on the spot costs more: 22.5 against 30.1 - they stay in line)
-      per_s = h->lds_step + deal_region;
-      h->lds_cycle_step = h->lds_step, h->cycle_no_defer = true;
+// The only place that knows which engine runs which dealing form: requests (h->req), what the engine can do (two to four players,
+// a CU's LDS, the batch's share of the chip) and the SK_DIAG switches -> h->form, k_cycle's workgroup shape and LDS, the default
+// interval.  Called by skyjo_vec_create and, through change_form(), by every option that changes a request; SKYJO_OPT_RECORD_LAYOUT
+// re-runs it for the LDS sizes alone.
+void resolve_form(skyjo_vec *h) {
+  const SkParams &P = h->P;
+  const int N = P.L.N;
+  const bool fixed_n = N >= 2 && N <= 4;
+  // k_cycle: S step + S dealing wavefronts per workgroup, S = what spreads the batch over the CUs (1 .. 4) or SKYJO_OPT_CYCLE_S; their
+  // LDS regions and the claim words must fit one CU (S = 1 always does: at most 32 + 15 KiB)
+  int S = h->req.cycle_s ? h->req.cycle_s : (P.tiles + h->ncu - 1) / h->ncu;
+  S = S < 1 ? 1 : (S > SK_CYCLE_MAX_S ? SK_CYCLE_MAX_S : S);
+  const int natural_s = S;
+  size_t region = h->lds_rollout;
+  bool no_defer = false;
+  if ((size_t)S * (h->lds_rollout + kDealLds) + 32 > kCuLds && (size_t)S * (h->lds_step + kDealLds) + 32 <= kCuLds && N <= 3 &&
+      !sk_diag_env("SKYJO_CYCLE_DEFER_ONLY")) {
+    // the direct observation of three players on a full chip: the CU's share of tiles fits without the card chunks of the deferred
+    // scoring (the games are then scored in the iteration they end: a slower step, but one round of workgroups - 31.0 against 23.5
+    // x 10^9 in line; four players, where scoring on the spot costs more: 22.5 against 30.1 - they stay in line)
+    region = h->lds_step, no_defer = true;
+  }
+  while (S > 1 && (size_t)S * (region + kDealLds) + 32 > kCuLds) S--;  // (fewer wavefronts per workgroup, more workgroups)
+  h->cycle_s = S;
+  if (h->rec_planar && !P.L.indirect) {
+    // the direct observation's wide records leave from registers in this layout: the staging area shrinks to the rare paths' 4 KiB of
+    // scratch, and where the card chunks of the deferred scoring did not fit beside it (three players on a full chip) they do now
+    const size_t base = h->lds_tile + 4096, with_defer = base + (size_t)N * 1024;
+    no_defer = (size_t)S * (with_defer + kDealLds) + 32 > kCuLds;
+    region = no_defer ? base : with_defer;
+  }
+  h->lds_cycle_step = region, h->lds_cycle = (size_t)S * (region + kDealLds) + 32;
+  h->cycle_deal_arg = kDealLds | (no_defer ? 1u << 29 : 0u);
+  if (const char *e = sk_diag_env("SKYJO_CYCLE_SPLIT")) h->cycle_deal_arg |= (uint32_t)(atoi(e) & 3) << 30;  // diagnostic: 1 = roles by SIMD parity, 2 = by SIMD pair
+  h->one_kernel_capable = fixed_n && h->lds_cycle <= kCuLds && !sk_diag_env("SKYJO_LDS_PAD");
+  // (the attribute belongs to the function, not to the handle: always the whole CU, so that engines of different batch sizes -
+  // different S - can live side by side in one process)
+  for (int planar = 0; planar < 2 && h->one_kernel_capable; planar++)
+    if (hipFuncSetAttribute((const void *)find_kernel(kCycleKernels, kernel_key(N, P.L.indirect != 0, planar != 0)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCuLds) != hipSuccess) {
+      (void)hipGetLastError();
+      h->one_kernel_capable = false;
     }
-    while (S > 1 && (size_t)S * per_s + 32 > 160 * 1024) S--;  // (fewer wavefronts per workgroup, more workgroups)
-    const size_t need = (size_t)S * per_s + 32;
-    const bool fits = fixed_n && need <= 160 * 1024 && !sk_diag_env("SKYJO_LDS_PAD");
-    h->lds_cycle = need, h->cycle_s = S;
-    h->merged_capable = fits;
-    if (fits) {
-      const void *fn = P.L.indirect ? (P.L.N == 2 ? (const void *)k_cycle<true, 2, false> : P.L.N == 3 ? (const void *)k_cycle<true, 3, false> : (const void *)k_cycle<true, 4, false>)
-                                    : (P.L.N == 2 ? (const void *)k_cycle<false, 2, false> : P.L.N == 3 ? (const void *)k_cycle<false, 3, false> : (const void *)k_cycle<false, 4, false>);
-      const void *fnp = P.L.indirect ? (P.L.N == 2 ? (const void *)k_cycle<true, 2, true> : P.L.N == 3 ? (const void *)k_cycle<true, 3, true> : (const void *)k_cycle<true, 4, true>)
-                                     : (P.L.N == 2 ? (const void *)k_cycle<false, 2, true> : P.L.N == 3 ? (const void *)k_cycle<false, 3, true> : (const void *)k_cycle<false, 4, true>);
-      // (the attribute belongs to the function, not to the handle: always the whole CU, so that engines of different batch sizes -
-      // different S - can live side by side in one process)
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-          (fnp && hipFuncSetAttribute(fnp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)) {
-        (void)hipGetLastError();
-        h->merged_capable = false;
-      }
+  // The engine's own choice: the one-kernel form wherever it fits (measured at 4 096 .. 65 536 games and two to four players: + 9 .. 32 %
+  // over the two-stream form, + 18 .. 57 % over dealing in line, EXPERIMENTS.md round 4).
+  // (Batches beyond four tiles per CU run in two or more rounds of workgroups - a workgroup's LDS fills its CU: 98 304 x 3 29.1
+  // against 23.8 in line, 131 072 x 3 34.0 against 21.0; counter-based deals 37.5 / 49.4 against 39.6 / 32.5: the one-kernel
+  // form still wins everywhere but at one and a half rounds of counter-based deals.  Not so where the LDS - not the batch - makes
+  // the workgroups smaller than a CU's share of the tiles, i.e. a full chip of four-player games or of the direct observation: S = 3,
+  // 342 workgroups in one and a third rounds, 25.5 against 30.0 and 17.5 against 23.6 in line.)
+  bool prefer_one = S == natural_s;
+  if (const char *e = sk_diag_env("SKYJO_MERGED")) prefer_one = atoi(e) != 0;
+  prefer_one = prefer_one && h->one_kernel_capable;
+  // Otherwise the dealing kernel runs beside the step kernel (own stream) when the batch leaves SIMDs free: up to 768 tiles of
+  // the 1024 one-wavefront-per-SIMD slots (three-player games, beside / in line, x 10^9 steps/s: 32 768: 17.1 / 15.5,
+  // 49 152: 23.1 / 22.6, 57 344: 25.2 / 26.1, 65 536: 20.3 / 29.0 - on a full chip the two kernels compete for the same
+  // vector ALUs), in line above that.
+  bool one = false, beside = false;
+  switch (h->req.overlap) {
+    case 0: break;
+    case 1: one = prefer_one, beside = !one; break;
+    case 2: beside = true; break;
+    case 3: one = h->one_kernel_capable; break;  // (the option refuses it where it is not)
+    default: {
+      const char *e = sk_diag_env("SKYJO_OVERLAP");
+      one = prefer_one && !e;
+      beside = !one && (e ? atoi(e) != 0 : P.tiles <= 768);
     }
-    // Default: the one-kernel form wherever it fits (measured at 4 096 .. 65 536 games and two to four players: + 9 .. 32 % over the
-    // two-stream form, + 18 .. 57 % over dealing in line, EXPERIMENTS.md round 4); SKYJO_MERGED=0 falls back to the older forms.
-    // (Batches beyond four tiles per CU run in two or more rounds of workgroups - a workgroup's LDS fills its CU: 98 304 x 3 29.1
-    // against 23.8 in line, 131 072 x 3 34.0 against 21.0; counter-based deals 37.5 / 49.4 against 39.6 / 32.5: the one-kernel
-    // form still wins everywhere but at one and a half rounds of counter-based deals.  Not so where the LDS - not the batch - makes
-    // the workgroups smaller than a CU's share of the tiles, i.e. a full chip of four-player games or of the direct observation: S = 3,
-    // 342 workgroups in one and a third rounds, 25.5 against 30.0 and 17.5 against 23.6 in line.)
-    h->prefer_merged = S == natural_s;
-    if (const char *e = sk_diag_env("SKYJO_MERGED")) h->prefer_merged = atoi(e) != 0;
-    h->merged = h->merged_capable && h->prefer_merged && !sk_diag_env("SKYJO_OVERLAP");
-    if (h->merged) h->overlap = false;  // (no second stream in this form)
+  }
+  h->form = one      ? DealForm::OneKernel
+            : beside ? (h->req.unpipelined ? DealForm::TwoStreamsScanPublish : DealForm::TwoStreamsPipelined)
+                     : (h->req.inline_work_list ? DealForm::InlineWorkList : DealForm::InlineScan);
+  h->interval_default = deal_interval_default(N, h->form, h->cycle_s);
+  if (h->auto_interval) h->deal_every_iters = h->interval_default;
+}
+
+// Every option that changes a request goes through here: nothing runs and nothing is in flight in the old form when the new one
+// takes over (the caller's stream may be a non-blocking one, so the device is synchronised before the null stream publishes).
+int change_form(skyjo_vec *h, const DealRequests &req) {
+  HIPCHK(hipDeviceSynchronize());
+  int rc = publish_deals(h, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  h->req = req;
+  resolve_form(h);
+  return SKYJO_OK;
 }
 
 }  // namespace
@@ -681,17 +722,10 @@ int skyjo_vec_create(const skyjo_vec_config *cfg, skyjo_vec **out) {
       h->raw_export = h->fast_host && P.tiles <= 4 && !sk_diag_env("SKYJO_NO_RAW_EXPORT");
     }
   }
-  // The dealing kernel runs beside the step kernel (own stream) when the batch leaves SIMDs free: up to 768 tiles of
-  // the 1024 one-wavefront-per-SIMD slots (three-player games, beside / in line, x 10^9 steps/s: 32 768: 17.1 / 15.5,
-  // 49 152: 23.1 / 22.6, 57 344: 25.2 / 26.1, 65 536: 20.3 / 29.0 - on a full chip the two kernels compete for the same
-  // vector ALUs), in line above that.  SKYJO_OPT_OVERLAP / SKYJO_OVERLAP override.
-  h->overlap = P.tiles <= 768;
-  if (const char *e = sk_diag_env("SKYJO_OVERLAP")) h->overlap = atoi(e) != 0;
   h->ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  configure_cycle(h, 0);
-  if (const char *e = sk_diag_env("SKYJO_FUSED_SCAN")) h->fused_scan = atoi(e) != 0;
-  if (const char *e = sk_diag_env("SKYJO_PIPELINED")) h->piped = atoi(e) != 0;
-  h->deal_every_iters = h->interval_default = deal_interval_default(cfg->num_players, h->overlap, h->piped, h->merged ? h->cycle_s : 0);
+  if (const char *e = sk_diag_env("SKYJO_FUSED_SCAN")) h->req.inline_work_list = atoi(e) == 0;  // (diagnostic builds: the options' initial values)
+  if (const char *e = sk_diag_env("SKYJO_PIPELINED")) h->req.unpipelined = atoi(e) == 0;
+  resolve_form(h);
   if (const char *e = sk_diag_env("SKYJO_DEAL_INTERVAL")) {
     const int v = atoi(e);
     if (v >= 1 && v <= 1024) h->deal_every_iters = v, h->auto_interval = false;
@@ -745,7 +779,7 @@ int skyjo_vec_seed(skyjo_vec *h, const uint64_t *seeds_host, uint64_t base_seed,
   HIPCHK(hipGetLastError());
   int rc;
   // set_seed deals immediately (skyjo.py:88): deal #0 becomes the live game, the following ones fill the bank
-  h->deal_inflight = false, h->inflight_piped = false;
+  h->inflight = InFlight::None;
   if ((rc = start_deals(h, s)) || (rc = publish_deals(h, s))) return rc;
   h->seeded = true;
   if ((rc = skyjo_vec_reset(h, nullptr, nullptr, stream))) return rc;
@@ -851,7 +885,7 @@ int skyjo_vec_snapshot_restore(skyjo_vec *h, const skyjo_vec_snapshot *sn, void 
   h->deal_tag = sn->deal_tag, h->P.deal_tag = sn->deal_tag, h->iter = sn->iter, h->iters_total = sn->iters_total;
   h->health_host[0] = sn->health[0], h->health_host[1] = sn->health[1];
   h->health_host[2] = 0;  // the restored device word is clean (snapshot_create refuses a voided run): so is the host's copy
-  h->deal_inflight = false, h->inflight_piped = false;
+  h->inflight = InFlight::None;
   h->raw_valid = false;
   return SKYJO_OK;
 }
@@ -893,12 +927,11 @@ int skyjo_vec_reset(skyjo_vec *h, const uint8_t *mask, void *records_out, void *
 
 static int step_once(skyjo_vec *h, const int32_t *actions, void *records_out, double *end_rew, uint8_t *end_flag, hipStream_t s,
                      uint8_t *raw_out = nullptr, bool planar_out = false) {
-  const bool due = h->pending_iters + 1 >= h->deal_every_iters, piped = piped_mode(h);
-  if (due && piped) plan_cycle(h);
+  const bool due = h->pending_iters + 1 >= h->deal_every_iters;
+  if (due && plans_ahead(h)) plan_cycle(h);
   int rc = launch_step(h, s, false, actions, (uint8_t *)records_out, nullptr, 1, 0, end_rew, end_flag, raw_out, 0, planar_out && records_out);
   if (rc) return rc;
-  if (due) return piped ? start_deals_piped(h, s) : start_deals(h, s);
-  return SKYJO_OK;
+  return due ? start_due_deals(h, s) : SKYJO_OK;
 }
 
 int skyjo_vec_step(skyjo_vec *h, const int32_t *actions, void *records_out, void *stream) {
@@ -973,26 +1006,26 @@ int skyjo_vec_rollout(skyjo_vec *h, int32_t iters, uint64_t policy_seed, void *r
   hipStream_t s = (hipStream_t)stream;
   uint8_t *rec = (uint8_t *)records_out;
   const bool planar = h->rec_planar;
-  if (planar && rec && !h->merged)
+  if (planar && rec && h->form != DealForm::OneKernel)
     return fail(SKYJO_E_STATE, "SKYJO_OPT_RECORD_LAYOUT = tile-planar needs the one-kernel dealing form (SKYJO_OPT_OVERLAP 3)");
   for (int done = 0; done < iters;) {
     int n = iters - done < kMaxRolloutChunk ? iters - done : kMaxRolloutChunk;
     // a launch ends where the next dealing run is due, so the cadence does not depend on how the caller slices its calls
     const int due = h->deal_every_iters - h->pending_iters;
     if (n > due) n = due > 0 ? due : 1;
-    const bool run_due = h->pending_iters + n >= h->deal_every_iters, piped = piped_mode(h);
+    const bool run_due = h->pending_iters + n >= h->deal_every_iters, planned = plans_ahead(h);
     // The one-kernel form keeps its tiles in LDS over several dealing cycles when the caller asks for that many iterations at once:
     // up to kMaxCyclesPerLaunch whole cycles in ONE launch (the cycle ends inside it are handled by the kernel: step_body, k_cycle)
     int cycles = 1;
     // (only where the kernel's cycle ends have a run to hand over: an engine that never deals ahead - SKYJO_OPT_NO_BANK - plans nothing,
     // and a cycle end inside its launch would publish and plan with a stale id: ADVICE r4)
-    if (h->merged && piped && run_due && h->pending_iters == 0) {
+    if (h->form == DealForm::OneKernel && planned && run_due && h->pending_iters == 0) {
       const int cap = h->max_cycles > 0 ? h->max_cycles : kMaxCyclesPerLaunch;
       cycles = (iters - done) / h->deal_every_iters;
       cycles = cycles < 1 ? 1 : (cycles > cap ? cap : cycles);
       n = cycles * h->deal_every_iters;
     }
-    if (run_due && piped) {
+    if (run_due && planned) {
       plan_cycle(h);
       const uint32_t first = h->deal_tag;  // the id of the first run planned by this launch; the kernel counts on from it
       for (int c = 1; c < cycles; c++) next_deal_tag(h, false);
@@ -1001,7 +1034,7 @@ int skyjo_vec_rollout(skyjo_vec *h, int32_t iters, uint64_t policy_seed, void *r
     int rc = launch_step(h, s, true, nullptr, rec, actions_out, n, policy_seed, nullptr, nullptr, nullptr, cycles > 1 ? h->deal_every_iters : 0);
     if (rc) return rc;
     done += n;
-    if (run_due && (rc = piped ? start_deals_piped(h, s) : start_deals(h, s))) return rc;
+    if (run_due && (rc = start_due_deals(h, s))) return rc;
     if (rec) rec += (size_t)n * (planar ? h->G : (size_t)h->P.B) * h->P.L.rec_bytes;
     if (actions_out) actions_out += (size_t)n * h->P.B;
   }
@@ -1429,7 +1462,7 @@ int skyjo_vec_rng_set_state(skyjo_vec *h, int32_t game, const uint32_t *key_host
   if (!h || !key_host || game < 0 || game >= h->P.B || pos < 0 || pos > 624) return fail(SKYJO_E_INVALID, "bad argument");
   GUARD(h);
   if (!h->seeded) return fail(SKYJO_E_STATE, "skyjo_vec_seed must be called first");
-  if (h->P.rng_mode != SKYJO_RNG_MT19937 || !h->no_bank)
+  if (h->P.rng_mode != SKYJO_RNG_MT19937 || !h->req.no_bank)
     return fail(SKYJO_E_STATE, "skyjo_vec_rng_set_state needs the MT19937 mode and SKYJO_OPT_NO_BANK (episodes dealt ahead would belong to the old stream)");
   hipStream_t s = (hipStream_t)stream;
   // numpy's (key, pos): the words from pos on are regenerated and unconsumed, everything is of one generation - in the
@@ -1445,7 +1478,7 @@ int skyjo_vec_rng_get_state(skyjo_vec *h, int32_t game, uint32_t *key_out_host, 
   if (!h || !key_out_host || !pos_out_host || game < 0 || game >= h->P.B) return fail(SKYJO_E_INVALID, "bad argument");
   GUARD(h);
   if (!h->seeded) return fail(SKYJO_E_STATE, "skyjo_vec_seed must be called first");
-  if (h->P.rng_mode != SKYJO_RNG_MT19937 || !h->no_bank)
+  if (h->P.rng_mode != SKYJO_RNG_MT19937 || !h->req.no_bank)
     return fail(SKYJO_E_STATE, "skyjo_vec_rng_get_state needs the MT19937 mode and SKYJO_OPT_NO_BANK");
   hipStream_t s = (hipStream_t)stream;
   int32_t packed = 0;
@@ -1515,11 +1548,11 @@ int skyjo_vec_get_option(const skyjo_vec *h, int option, int64_t *value_out) {
   if (!h || !value_out) return fail(SKYJO_E_INVALID, "null argument");
   switch (option) {
     case SKYJO_OPT_DEAL_INTERVAL: *value_out = h->deal_every_iters; return SKYJO_OK;
-    case SKYJO_OPT_OVERLAP: *value_out = h->merged ? 3 : h->overlap ? 2 : 0; return SKYJO_OK;
-    case SKYJO_OPT_NO_BANK: *value_out = h->no_bank ? 1 : 0; return SKYJO_OK;
+    case SKYJO_OPT_OVERLAP: *value_out = h->form == DealForm::OneKernel ? 3 : uses_deal_stream(h->form) ? 2 : 0; return SKYJO_OK;
+    case SKYJO_OPT_NO_BANK: *value_out = h->req.no_bank ? 1 : 0; return SKYJO_OK;
     case SKYJO_OPT_RECORD_LAYOUT: *value_out = h->rec_planar_all ? SKYJO_REC_TILE_PLANAR_ALL : h->rec_planar ? SKYJO_REC_TILE_PLANAR : SKYJO_REC_ROW_MAJOR; return SKYJO_OK;
-    case SKYJO_OPT_INLINE_WORK_LIST: *value_out = h->fused_scan ? 0 : 1; return SKYJO_OK;
-    case SKYJO_OPT_UNPIPELINED: *value_out = h->piped ? 0 : 1; return SKYJO_OK;
+    case SKYJO_OPT_INLINE_WORK_LIST: *value_out = h->req.inline_work_list ? 1 : 0; return SKYJO_OK;
+    case SKYJO_OPT_UNPIPELINED: *value_out = h->req.unpipelined ? 1 : 0; return SKYJO_OK;
     case SKYJO_OPT_CYCLE_S: *value_out = h->cycle_s; return SKYJO_OK;
     case SKYJO_OPT_MAX_CYCLES_PER_LAUNCH: *value_out = h->max_cycles > 0 ? h->max_cycles : kMaxCyclesPerLaunch; return SKYJO_OK;
     default: return fail(SKYJO_E_INVALID, "unknown option");
@@ -1529,61 +1562,44 @@ int skyjo_vec_get_option(const skyjo_vec *h, int option, int64_t *value_out) {
 int skyjo_vec_set_option(skyjo_vec *h, int option, int64_t value) {
   if (!h) return fail(SKYJO_E_INVALID, "null handle");
   GUARD(h);
+  DealRequests req = h->req;
   switch (option) {
     case SKYJO_OPT_DEAL_INTERVAL:
       if (value < 1 || value > 1024) return fail(SKYJO_E_INVALID, "deal interval must be in 1..1024");
       h->deal_every_iters = (int)value, h->auto_interval = false;
       return SKYJO_OK;
-    case SKYJO_OPT_OVERLAP: {
-      int rc = publish_deals(h, nullptr);  // drain the pipeline before changing its shape
-      if (rc) return rc;
-      HIPCHK(hipDeviceSynchronize());
+    case SKYJO_OPT_OVERLAP:
       // 0: in line; 1: beside the step kernel, in the form this engine prefers; 2: the two-stream form; 3: the one-kernel form (k_cycle)
       if (value < 0 || value > 3) return fail(SKYJO_E_INVALID, "SKYJO_OPT_OVERLAP takes 0 .. 3");
-      if (value == 3 && !h->merged_capable)
-        return fail(SKYJO_E_INVALID, "the one-kernel form needs two to four players");
-      h->merged = value == 3 || (value == 1 && h->merged_capable && h->prefer_merged);
-      h->overlap = value != 0 && !h->merged;
-      h->interval_default = deal_interval_default(h->P.L.N, h->overlap, h->piped, h->merged ? h->cycle_s : 0);
-      if (h->auto_interval) h->deal_every_iters = h->interval_default;
-      return SKYJO_OK;
-    }
+      if (value == 3 && !h->one_kernel_capable) return fail(SKYJO_E_INVALID, "the one-kernel form needs two to four players");
+      req.overlap = (int)value;
+      return change_form(h, req);
     case SKYJO_OPT_NO_BANK:
       if (h->seeded) return fail(SKYJO_E_STATE, "SKYJO_OPT_NO_BANK must be set before skyjo_vec_seed");
-      h->no_bank = value != 0;
+      h->req.no_bank = value != 0;
       return SKYJO_OK;
     case SKYJO_OPT_RECORD_LAYOUT:
       if (value != SKYJO_REC_ROW_MAJOR && value != SKYJO_REC_TILE_PLANAR && value != SKYJO_REC_TILE_PLANAR_ALL)
         return fail(SKYJO_E_INVALID, "SKYJO_OPT_RECORD_LAYOUT takes SKYJO_REC_ROW_MAJOR, SKYJO_REC_TILE_PLANAR or SKYJO_REC_TILE_PLANAR_ALL");
-      if (value != SKYJO_REC_ROW_MAJOR && !h->merged_capable)
+      if (value != SKYJO_REC_ROW_MAJOR && !h->one_kernel_capable)
         return fail(SKYJO_E_INVALID, "the tile-planar record layout exists for the one-kernel form of the fused rollout (two to four players)");
       if (value == SKYJO_REC_TILE_PLANAR_ALL && !h->P.L.indirect)
         return fail(SKYJO_E_INVALID, "SKYJO_REC_TILE_PLANAR_ALL: reset / observe / step write tile-planar records of the indirect observation only");
       h->rec_planar = value != SKYJO_REC_ROW_MAJOR;
       h->rec_planar_all = value == SKYJO_REC_TILE_PLANAR_ALL;
+      resolve_form(h);  // (k_cycle's LDS regions depend on the layout)
       return SKYJO_OK;
     case SKYJO_OPT_INLINE_WORK_LIST:
-      h->fused_scan = value == 0;
-      return SKYJO_OK;
-    case SKYJO_OPT_UNPIPELINED: {
-      int rc = publish_deals(h, nullptr);  // drain the pipeline before changing its shape
-      if (rc) return rc;
-      HIPCHK(hipDeviceSynchronize());
-      h->piped = value == 0;
-      h->interval_default = deal_interval_default(h->P.L.N, h->overlap, h->piped, h->merged ? h->cycle_s : 0);
-      if (h->auto_interval) h->deal_every_iters = h->interval_default;
-      return SKYJO_OK;
-    }
-    case SKYJO_OPT_CYCLE_S: {
+      req.inline_work_list = value != 0;
+      return change_form(h, req);
+    case SKYJO_OPT_UNPIPELINED:
+      req.unpipelined = value != 0;
+      return change_form(h, req);
+    case SKYJO_OPT_CYCLE_S:
       if (h->seeded) return fail(SKYJO_E_STATE, "SKYJO_OPT_CYCLE_S must be set before skyjo_vec_seed");
       if (value < 0 || value > SK_CYCLE_MAX_S) return fail(SKYJO_E_INVALID, "SKYJO_OPT_CYCLE_S takes 0 (the batch's share) .. 4");
-      const bool was = h->merged;
-      configure_cycle(h, (int)value);
-      if (was && !h->merged_capable) return fail(SKYJO_E_INVALID, "that many step regions do not fit a compute unit's LDS");
-      h->interval_default = deal_interval_default(h->P.L.N, h->overlap, h->piped, h->merged ? h->cycle_s : 0);
-      if (h->auto_interval) h->deal_every_iters = h->interval_default;
-      return SKYJO_OK;
-    }
+      req.cycle_s = (int)value;  // (a value whose regions do not fit a CU's LDS is lowered until they do: resolve_form)
+      return change_form(h, req);
     case SKYJO_OPT_MAX_CYCLES_PER_LAUNCH:
       if (value < 1 || value > kMaxCyclesPerLaunch) return fail(SKYJO_E_INVALID, "SKYJO_OPT_MAX_CYCLES_PER_LAUNCH takes 1 .. 16");
       h->max_cycles = (int)value;

@@ -61,3 +61,32 @@ def test_the_library_ignores_the_old_environment_variables(monkeypatch):
     assert e.dealing_form() == "one kernel" and _get(e, _lib.OPT_CYCLE_S) == 1 and e.deal_interval() != 7
     assert _get(e, _lib.OPT_INLINE_WORK_LIST) == 0 and _get(e, _lib.OPT_UNPIPELINED) == 0
     e.close()
+
+
+@pytest.mark.parametrize("overlap,form", [(0, "in line"), (2, "two streams")])
+def test_cycle_s_keeps_an_explicit_dealing_form(overlap, form):
+    """SKYJO_OPT_CYCLE_S re-sizes the one-kernel form; it does not take back an earlier SKYJO_OPT_OVERLAP (it used to: the form fell
+    back to the engine's own choice).  An engine treated so rolls out what an untouched one does."""
+    import torch
+    from skyjo_rl_amd import SkyjoVecEnv, _lib
+
+    B, N, K = 4096, 3, 200
+    outs = []
+    for treated in (False, True):
+        e = SkyjoVecEnv(B, num_players=N, auto_reset=True)
+        assert e.dealing_form() == "one kernel"
+        if treated:
+            e.set_overlap(overlap)
+            assert e.dealing_form() == form
+            e.set_option(_lib.OPT_CYCLE_S, 2)
+            assert e.dealing_form() == form and _get(e, 2) == overlap and _get(e, _lib.OPT_CYCLE_S) == 2
+        e.seed(None, 5)
+        rec, act = e.new_records(K), torch.empty((K, B), dtype=torch.int32, device="cuda")
+        for _ in range(3):
+            e.rollout(K, policy_seed=2, records=rec, actions=act)
+        c = e.counters()
+        assert e.dealing_form() == (form if treated else "one kernel")
+        outs.append((rec.clone(), act.clone(), {k: c[k] for k in ("steps", "episodes", "resets", "sum_len")}))
+        e.close()
+    assert outs[0][2]["episodes"] > 0
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]) and outs[0][2] == outs[1][2]

@@ -331,6 +331,91 @@ def test_mixed_calls_while_dealing_runs_are_in_flight(seed, N, B):
     eng.close()
 
 
+@pytest.mark.parametrize("seed,N,B", [(11, 3, 1024), (12, 2, 700), (15, 4, 2048)])
+def test_mixed_calls_while_the_dealing_variants_are_toggled(seed, N, B):
+    """test_mixed_calls_while_dealing_runs_are_in_flight with two more operations in the draw: SKYJO_OPT_UNPIPELINED and
+    SKYJO_OPT_INLINE_WORK_LIST change between calls, i.e. on an engine that has runs in flight and steps queued (elsewhere they are
+    only ever set on an idle one).  Every change drains what the form before it left; after every call the engine shows what the
+    oracle shows.  (The seeds are ones whose draw - it does not depend on the engine - has SKYJO_OPT_UNPIPELINED on while the form
+    is "two streams" and SKYJO_OPT_INLINE_WORK_LIST on while it is "in line"; the last assertion holds the draw to that.)"""
+    import ctypes as C
+
+    import torch
+    from skyjo_rl_amd import _lib
+
+    cfg = dict(num_players=N, score_penalty=2.0, observe_other_player_indirect=True, mean_reward=1.0,
+               reward_refunded=0.001, rng_mode=0, auto_reset=True)
+    eng = _engine(B, **cfg)
+    ora = _oracle_vec(num_envs=B, **cfg)
+    eng.seed(None, 78)
+    ora.seed(None, 78)
+    rng = np.random.default_rng(seed)
+    pol = 0
+    seen = set()
+
+    def get(opt):
+        v = C.c_int64()
+        _lib.check(eng._L.skyjo_vec_get_option(eng._h, int(opt), C.byref(v)))
+        return int(v.value)
+
+    def same(tag):
+        obs, mask, agent, phase = ora.observe()
+        o = eng.observe_host()
+        np.testing.assert_array_equal(o.observations, obs, err_msg=tag)
+        np.testing.assert_array_equal(o.action_mask, mask, err_msg=tag)
+        np.testing.assert_array_equal(o.agent, agent, err_msg=tag)
+        np.testing.assert_array_equal(o.phase, phase, err_msg=tag)
+
+    for r in range(90):
+        op = rng.choice(["rollout", "rollout", "rollout", "step", "reset", "seed_one", "snapshot", "overlap", "interval",
+                         "unpipelined", "work_list"])
+        if op == "rollout":
+            k = int(rng.integers(1, 120))
+            pol += 1
+            act = torch.empty((k, B), dtype=torch.int32, device="cuda")
+            eng.rollout(k, policy_seed=pol, actions=act)
+            np.testing.assert_array_equal(act.cpu().numpy(), ora.rollout(k, pol, record_actions=True), err_msg=f"round {r}")
+        elif op == "step":
+            for _ in range(int(rng.integers(1, 6))):
+                obs, mask, agent, phase = ora.observe()
+                acts = np.argmax(rng.random((B, 26)) * mask, axis=1).astype(np.int32)
+                ora.step(acts)
+                o = eng.step_host(acts)
+                np.testing.assert_array_equal(o.status, ora.status, err_msg=f"round {r}")
+                np.testing.assert_array_equal(o.done, ora.dones, err_msg=f"round {r}")
+        elif op == "reset":
+            m = (rng.random(B) < 0.05).astype(np.uint8)
+            ora.reset(m)
+            eng.reset_host(m)
+        elif op == "seed_one":
+            g, v = int(rng.integers(0, B)), int(rng.integers(0, 1 << 30))
+            ora.seed_one(g, v)
+            eng.seed_one(g, v)
+        elif op == "snapshot":
+            snap = eng.snapshot()
+            eng.rollout(int(rng.integers(1, 60)), policy_seed=999)
+            eng.restore(snap)
+        elif op == "overlap":
+            eng.set_overlap(int(rng.choice([0, 1, 2, 3])))
+        elif op == "interval":
+            eng.set_deal_interval(int(rng.integers(4, 100)))
+        else:
+            opt = _lib.OPT_UNPIPELINED if op == "unpipelined" else _lib.OPT_INLINE_WORK_LIST
+            val = int(rng.integers(0, 2))
+            form = eng.dealing_form()
+            eng.set_option(opt, val)
+            assert get(opt) == val and eng.dealing_form() == form  # (the variants never move an engine between in line / two streams / one kernel)
+        seen.add((eng.dealing_form(), get(_lib.OPT_UNPIPELINED), get(_lib.OPT_INLINE_WORK_LIST)))
+        same(f"round {r} after {op}")
+    c, oc = eng.counters(), ora.counters()
+    for k in ("steps", "episodes", "resets", "sum_len"):
+        assert c[k] == oc[k], (k, c[k], oc[k])
+    assert c["episodes"] > 0
+    # the draw reached both variants of the older forms, not only the defaults
+    assert {f for f, u, w in seen if u} >= {"two streams"} and {f for f, u, w in seen if w} >= {"in line"}, seen
+    eng.close()
+
+
 def test_headline_size_properties():
     """BASELINE config 3 (65 536 three-player games): size-independent invariants + an oracle-checked subset."""
     import torch
