@@ -10,7 +10,9 @@ an episode).  Steps of episodes that did not finish inside the buffer carry no r
 """
 import torch
 
+from skyjo_rl_amd._lib import TGT_HAS_TARGET
 from skyjo_rl_amd.action_mask_model import FLOAT_MIN, FusedNet
+from skyjo_rl_amd.rollout import compute_targets
 
 
 @torch.no_grad()
@@ -34,12 +36,18 @@ def compute_returns(buf):
     return returns, mask
 
 
-def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_coef=1.0, seed=0):
+def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_coef=1.0, seed=0, gae=None):
     """Clipped-surrogate PPO epochs over the buffer (RLlib defaults: clip_param 0.3, vf_loss_coeff 1.0).  Returns the mean
-    losses of the first and the last epoch."""
+    losses of the first and the last epoch.  ``gae``: None - Monte-Carlo returns of the episodes that ended inside the buffer
+    (``compute_returns``); (gamma, lambda) - advantages, value targets and the row mask of ``rollout.compute_targets`` (one
+    native call; rows of unfinished episodes take part, bootstrapped from the value estimates)."""
     v = buf.views()
     T = buf.T
-    returns, mask = compute_returns(buf)
+    if gae is None:
+        returns, mask = compute_returns(buf)
+    else:
+        compute_targets(buf, gamma=gae[0], lam=gae[1])
+        returns, mask = buf.value_targets, (buf.target_flags & TGT_HAS_TARGET) != 0
     idx = mask.reshape(-1).nonzero().squeeze(1)
     obs = v.observations[:T].reshape(-1, v.observations.shape[-1])
     am = v.action_mask[:T].reshape(-1, 26)
@@ -47,7 +55,7 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
     logp_old = buf.logp.reshape(-1)
     val_old = buf.values[:T].reshape(-1)
     ret = returns.reshape(-1)
-    adv_all = ret - val_old
+    adv_all = ret - val_old if gae is None else buf.advantages.reshape(-1)
     mean, std = adv_all[idx].mean(), adv_all[idx].std().clamp_min(1e-6)
     gen = torch.Generator(device=idx.device).manual_seed(seed)
     stats = []

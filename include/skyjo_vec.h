@@ -406,6 +406,27 @@ typedef struct skyjo_vec_rollout_buffers {
 int skyjo_vec_model_rollout(skyjo_vec *h, const skyjo_vec_mlp *policy, const skyjo_vec_mlp *value, int32_t T, uint64_t seed,
                             uint64_t first_ticket, int32_t no_masking, const skyjo_vec_rollout_buffers *buffers, void *stream);
 
+/* Learner targets of a rollout buffer, on device: what RLlib's PPO attaches to the sample batches of the reference's trainer
+ * (rlskyjo/models/train_model_simple_rllib.py:22-59) - `advantages` and `value_targets` by GAE(gamma, lambda) per agent trajectory -
+ * computed for every row (t, game) of the columns skyjo_vec_model_rollout has written, one kernel, one lane per game walking
+ * t = T - 1 .. 0 with per-seat carries (the seat that acts changes from row to row; DESIGN.md 4 has the recursion and its
+ * operation order, which is part of the definition: float32, no fused multiply-add).
+ *   records        [T+1] records in `layout` (SKYJO_REC_ROW_MAJOR: [T+1][num_envs][record_bytes]; SKYJO_REC_TILE_PLANAR:
+ *                  [T+1][tiles][P][64][16], read in place); only the agent and done bytes are read
+ *   values         float32 [T+1][num_envs][value_stride], component 0 is used; [T] bootstraps the seat records[T] expects
+ *   final_rewards  double [T][num_envs][num_players], read only where episode_end uint8 [T][num_envs] is set
+ *   gamma, lambda  in [0, 1]
+ *   advantages_out, value_targets_out, returns_out  float32 [T][num_envs];  flags_out uint8 [T][num_envs], SKYJO_TGT_* bits
+ * returns_out is the final reward of the acting seat's episode where that episode ended inside the buffer (0 elsewhere).  A row whose
+ * record shows done (a re-deal / no-op, not a transition) gets zeros and no flag.  A seat's last action inside the buffer in an episode
+ * that did not end there serves as the bootstrap of the seat's earlier actions and has no target itself - except for the seat
+ * records[T] expects, whose bootstrap is values[T]. */
+#define SKYJO_TGT_HAS_TARGET 1    /* advantages_out / value_targets_out are defined for the row */
+#define SKYJO_TGT_EPISODE_KNOWN 2 /* the row is a transition of an episode that ended inside the buffer: returns_out is its seat's final reward */
+int skyjo_vec_rollout_targets(skyjo_vec *h, const void *records, int32_t layout, int32_t T, const float *values, int32_t value_stride,
+                              const double *final_rewards, const uint8_t *episode_end, float gamma, float lambda,
+                              float *advantages_out, float *value_targets_out, float *returns_out, uint8_t *flags_out, void *stream);
+
 /* host-pointer conveniences for small batches (single-game AEC view): synchronous.  Up to 4096 games they go through
  * host-mapped memory (one launch + one synchronisation per call, no copies), and step_host / reset_host bring every game's
  * state and rewards back with the records: skyjo_vec_get_state and skyjo_vec_get_rewards_host right after them cost no

@@ -74,6 +74,7 @@ class RolloutBuffers(C.Structure):
 
 # option ids / record layouts of include/skyjo_vec.h
 OPT_RECORD_LAYOUT, REC_ROW_MAJOR, REC_TILE_PLANAR, REC_TILE_PLANAR_ALL = 6, 0, 1, 2
+TGT_HAS_TARGET, TGT_EPISODE_KNOWN = 1, 2  # SKYJO_TGT_*: bits of skyjo_vec_rollout_targets' flags column
 OPT_INLINE_WORK_LIST, OPT_UNPIPELINED, OPT_CYCLE_S, OPT_MAX_CYCLES_PER_LAUNCH = 7, 8, 9, 10
 
 # name -> (restype, argtypes); this table is also what tests/test_capi_symbols.py checks against the header
@@ -105,6 +106,7 @@ SIGNATURES = {
     "skyjo_vec_mlp_act_value_layout": (C.c_int, [VP, VP, VP, VP, I32, I64, U64, U64, I32, VP, VP, VP, VP, VP]),
     "skyjo_vec_step_collect": (C.c_int, [VP, VP, VP, VP, VP, VP]),
     "skyjo_vec_model_rollout": (C.c_int, [VP, VP, VP, I32, U64, U64, I32, C.POINTER(RolloutBuffers), VP]),
+    "skyjo_vec_rollout_targets": (C.c_int, [VP, VP, I32, I32, VP, I32, VP, VP, C.c_float, C.c_float, VP, VP, VP, VP, VP]),
     "skyjo_vec_rewards_ptr": (VP, [VP]),
     "skyjo_vec_scores_ptr": (VP, [VP]),
     "skyjo_vec_done_ptr": (VP, [VP]),

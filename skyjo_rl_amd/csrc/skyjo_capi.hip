@@ -13,6 +13,7 @@
 
 #include "skyjo_device.h"
 #include "skyjo_policy.h"
+#include "skyjo_targets.h"
 
 // Measurement switches (environment variables: tools/dev/README.md) exist in -DSK_DIAG builds only; the shipped library reads no
 // environment variable at all - what a caller or a test may choose is an option of skyjo_vec_set_option.
@@ -1283,6 +1284,37 @@ int skyjo_vec_episode_ends_layout(skyjo_vec *h, const void *records, int32_t lay
 }
 int skyjo_vec_episode_ends(skyjo_vec *h, const void *records, double *final_rewards_out, uint8_t *episode_end_out, void *stream) {
   return skyjo_vec_episode_ends_layout(h, records, SKYJO_REC_ROW_MAJOR, final_rewards_out, episode_end_out, stream);
+}
+
+// ---- learner targets of a rollout buffer (include/skyjo_vec.h: skyjo_vec_rollout_targets; the kernel: skyjo_targets.h) ----
+int skyjo_vec_rollout_targets(skyjo_vec *h, const void *records, int32_t layout, int32_t T, const float *values, int32_t value_stride,
+                              const double *final_rewards, const uint8_t *episode_end, float gamma, float lambda, float *advantages_out,
+                              float *value_targets_out, float *returns_out, uint8_t *flags_out, void *stream) {
+  if (!h || !records || !values || !final_rewards || !episode_end || !advantages_out || !value_targets_out || !returns_out || !flags_out)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_targets: null argument");
+  if (T < 1 || value_stride < 1) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_targets: T and value_stride must be at least 1");
+  if (!(gamma >= 0.f && gamma <= 1.f) || !(lambda >= 0.f && lambda <= 1.f))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_targets: gamma and lambda must lie in [0, 1]");
+  if (layout != SKYJO_REC_ROW_MAJOR && layout != SKYJO_REC_TILE_PLANAR) return fail(SKYJO_E_INVALID, "layout must be SKYJO_REC_ROW_MAJOR or SKYJO_REC_TILE_PLANAR");
+  GUARD(h);
+  const SkLayout &L = h->P.L;
+  SkTargetsArgs a{};
+  a.rec = (const uint8_t *)records, a.values = values, a.rewards = final_rewards, a.end = episode_end;
+  a.adv = advantages_out, a.vt = value_targets_out, a.ret = returns_out, a.flags = flags_out;
+  a.planar = layout == SKYJO_REC_TILE_PLANAR;
+  a.rec_stride = a.planar ? (long long)h->G : (long long)h->P.B;
+  a.B = h->P.B, a.T = T, a.N = L.N, a.vstride = value_stride, a.rec_bytes = L.rec_bytes;
+  a.off_agent = L.Dp + 26, a.off_done = L.Dp + 28;
+  a.gamma = gamma, a.gl = gamma * lambda;  // (float32 product, rounded once: part of the definition)
+  const dim3 grid((h->P.B + SK_TGT_LANES - 1) / SK_TGT_LANES), block(SK_TGT_LANES);
+  switch (L.N) {
+    case 2: hipLaunchKernelGGL(k_rollout_targets<2>, grid, block, 0, (hipStream_t)stream, a); break;
+    case 3: hipLaunchKernelGGL(k_rollout_targets<3>, grid, block, 0, (hipStream_t)stream, a); break;
+    case 4: hipLaunchKernelGGL(k_rollout_targets<4>, grid, block, 0, (hipStream_t)stream, a); break;
+    default: hipLaunchKernelGGL(k_rollout_targets<0>, grid, block, 0, (hipStream_t)stream, a); break;
+  }
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
 }
 
 int skyjo_vec_get_counters(skyjo_vec *h, skyjo_vec_counters *out, void *stream) {

@@ -6,7 +6,9 @@ between them.  ``collect_stepwise`` is the same loop made one launch at a time f
 ``skyjo_vec_step_collect``): same bits, used by the tests.  What a learner needs per step of the acting seat
 (``rlskyjo/models/train_model_simple_rllib.py:22-59`` has RLlib collect the same columns): observation / action mask (inside the
 records), action, log-probability, value estimate, the acting agent, done flags and - at episode ends - the final rewards of
-skyjo_env.py:293-312 for every seat.  ``RolloutBuffer.valid`` tells a learner which rows are transitions at all.
+skyjo_env.py:293-312 for every seat.  ``RolloutBuffer.valid`` tells a learner which rows are transitions at all.  ``compute_targets`` adds what RLlib's PPO attaches to those
+batches - ``advantages`` and ``value_targets`` by GAE per agent trajectory - in one more native call on the buffer as it lies
+(``skyjo_vec_rollout_targets``).
 """
 import ctypes as C
 
@@ -79,4 +81,27 @@ def collect_stepwise(env, policy, value, buf, seed=0, first_ticket=0, first_reco
         _lib.check(L.skyjo_vec_step_collect(env._h, vp(buf.actions[t]), vp(buf.records[t + 1]), vp(buf.final_rewards[t]),
                                             vp(buf.episode_end[t]), env._stream()))
     value(buf.records[buf.T], out=buf.values[buf.T], planar=buf.planar)
+    return buf
+
+
+@torch.no_grad()
+def compute_targets(buf, gamma=0.99, lam=1.0):
+    """Learner targets of a filled buffer in one native call (``skyjo_vec_rollout_targets``; RLlib's PPO defaults, which the
+    reference's script leaves as they are: gamma 0.99, lambda 1.0): per-seat GAE over the T x B rows, read in the buffer's own
+    layout - a tile-planar buffer is not unpacked.  Adds to ``buf`` (allocated on first use, refilled afterwards):
+    ``advantages`` / ``value_targets`` / ``returns`` float32 [T, B] and ``target_flags`` uint8 [T, B] (bit ``_lib.TGT_HAS_TARGET``:
+    the row has an advantage and a value target; bit ``_lib.TGT_EPISODE_KNOWN``: the row is a transition whose episode ended
+    inside the buffer and ``returns`` is its seat's final reward).  Returns ``buf``."""
+    L = _lib.load()
+    if getattr(buf, "advantages", None) is None:
+        dev = buf.actions.device
+        buf.advantages = torch.empty((buf.T, buf.B), dtype=torch.float32, device=dev)
+        buf.value_targets = torch.empty((buf.T, buf.B), dtype=torch.float32, device=dev)
+        buf.returns = torch.empty((buf.T, buf.B), dtype=torch.float32, device=dev)
+        buf.target_flags = torch.empty((buf.T, buf.B), dtype=torch.uint8, device=dev)
+    vp = lambda t: t.data_ptr()
+    _lib.check(L.skyjo_vec_rollout_targets(buf._env._h, vp(buf.records), _lib.REC_TILE_PLANAR if buf.planar else _lib.REC_ROW_MAJOR, buf.T,
+                                           vp(buf.values), buf.values.shape[-1], vp(buf.final_rewards), vp(buf.episode_end),
+                                           float(gamma), float(lam), vp(buf.advantages), vp(buf.value_targets), vp(buf.returns),
+                                           vp(buf.target_flags), buf._env._stream()))
     return buf
