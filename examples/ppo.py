@@ -12,7 +12,7 @@ import torch
 
 from skyjo_rl_amd._lib import TGT_HAS_TARGET
 from skyjo_rl_amd.action_mask_model import FLOAT_MIN, FusedNet
-from skyjo_rl_amd.rollout import compute_targets
+from skyjo_rl_amd.rollout import compute_targets, minibatches, select_rows
 
 
 @torch.no_grad()
@@ -36,11 +36,46 @@ def compute_returns(buf):
     return returns, mask
 
 
-def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_coef=1.0, seed=0, gae=None):
+def _ppo_update_native(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae):
+    """``ppo_update(..., native_batches=True)``: the same epochs on minibatches the package builds on the buffer as it lies."""
+    compute_targets(buf, gamma=gae[0], lam=gae[1])
+    sel = select_rows(buf, TGT_HAS_TARGET)
+    norm = (sel.mean, max(sel.std, 1e-6))
+    gen = torch.Generator(device=buf.actions.device).manual_seed(seed)
+    stats = []
+    for ep in range(epochs):
+        tot = {"policy_loss": 0.0, "vf_loss": 0.0, "kl": 0.0, "n": 0}
+        for mb in minibatches(buf, minibatch, generator=gen, normalize=norm, selection=sel):
+            logits = model.policy(mb.observations) + mb.log_mask  # action_mask_model.py:70-71
+            logp = torch.log_softmax(logits, -1).gather(1, mb.actions.unsqueeze(1)).squeeze(1)
+            value = model.value(mb.observations).squeeze(-1)
+            ratio = torch.exp(logp - mb.logp)
+            pl = -torch.min(ratio * mb.advantages, torch.clamp(ratio, 1 - clip, 1 + clip) * mb.advantages).mean()
+            vl = ((value - mb.value_targets) ** 2).mean()
+            loss = pl + vf_coef * vl
+            optimizer.zero_grad(set_to_none=True)
+            loss.backward()
+            optimizer.step()
+            n = mb.actions.numel()
+            tot["policy_loss"] += float(pl.detach()) * n
+            tot["vf_loss"] += float(vl.detach()) * n
+            tot["kl"] += float((mb.logp - logp).mean().detach()) * n
+            tot["n"] += n
+        stats.append({k: tot[k] / max(tot["n"], 1) for k in ("policy_loss", "vf_loss", "kl")})
+    return {"first": stats[0], "last": stats[-1], "transitions": sel.count}
+
+
+def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_coef=1.0, seed=0, gae=None, native_batches=False):
     """Clipped-surrogate PPO epochs over the buffer (RLlib defaults: clip_param 0.3, vf_loss_coeff 1.0).  Returns the mean
     losses of the first and the last epoch.  ``gae``: None - Monte-Carlo returns of the episodes that ended inside the buffer
     (``compute_returns``); (gamma, lambda) - advantages, value targets and the row mask of ``rollout.compute_targets`` (one
-    native call; rows of unfinished episodes take part, bootstrapped from the value estimates)."""
+    native call; rows of unfinished episodes take part, bootstrapped from the value estimates).  ``native_batches`` (needs
+    ``gae``): the minibatches come from ``rollout.minibatches`` - row selection, advantage moments and the gather in native calls
+    on the buffer as it lies, no ``buf.views()`` - instead of the torch expressions below."""
+    if native_batches:
+        if gae is None:
+            raise ValueError("native_batches=True needs gae=(gamma, lambda)")
+        return _ppo_update_native(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae)
     v = buf.views()
     T = buf.T
     if gae is None:

@@ -427,6 +427,43 @@ int skyjo_vec_rollout_targets(skyjo_vec *h, const void *records, int32_t layout,
                               const double *final_rewards, const uint8_t *episode_end, float gamma, float lambda,
                               float *advantages_out, float *value_targets_out, float *returns_out, uint8_t *flags_out, void *stream);
 
+/* Learner minibatches of a rollout buffer, on device: which rows take part, and the rows of one minibatch as the dense tensors a
+ * learner feeds its model - both read the buffer as it lies (DESIGN.md 4 has the definitions).
+ *
+ * skyjo_vec_rollout_select: the rows r of a flags column (in practice flags_out of skyjo_vec_rollout_targets seen as [T * num_envs]) with
+ * (flags[r] & require_bits) == require_bits, in ascending order - a stable compaction, what torch.nonzero gives - and the moments of
+ * their advantages.  Three launches (per-block counts, a scan of the block counts in one workgroup, the scatter), none waits for
+ * another workgroup; the sums have a fixed reduction shape and use no atomics: the same input gives the same bits on every call.
+ *   flags         uint8 [n_rows];  require_bits in 1 .. 255
+ *   advantages    float32 [n_rows] or NULL
+ *   index_out     int64 [n_rows]: the first *count_out entries are written
+ *   count_out     int64 [1] (device): the number of selected rows; 0 is a valid result
+ *   moments_out   double [2] (device; NULL iff advantages is NULL): the sum of a and the sum of a * a over the selected rows, every a
+ *                 widened to double first; both 0.0 when no row is selected
+ * n_rows == 0 writes count 0 and zero moments.  The block scratch belongs to the handle (allocated on first use, grown when needed). */
+int skyjo_vec_rollout_select(skyjo_vec *h, const uint8_t *flags, int64_t n_rows, int32_t require_bits,
+                             const float *advantages /* may be NULL */, int64_t *index_out /* [n_rows] */,
+                             int64_t *count_out /* device, 1 */, double *moments_out /* device, 2; NULL iff advantages is NULL */,
+                             void *stream);
+/* skyjo_vec_rollout_gather: the rows index[0 .. m) of the buffer - row ids r = t * num_envs + b, 0 <= r < T * num_envs, in any order,
+ * repeats allowed (a learner passes a shuffled slice of the selection) - as dense [m]-major outputs, one kernel:
+ *   records        the buffer's records in `layout` (as for skyjo_vec_rollout_targets; row r is record b of step t), 16-byte aligned
+ *   actions int32, logp / advantages / value_targets float32 [T][num_envs];  values float32 [T (+ 1)][num_envs][value_stride]
+ *   obs_out            float32 [m][obs_dim]  (float)(int8) of the record's observation bytes; 16-byte aligned
+ *   logmask_out        float32 [m][26]       0.0f where the action-mask byte is non-zero, -FLT_MAX elsewhere: what
+ *                                            clamp(log(action_mask), min=FLOAT_MIN) of action_mask_model.py:70 yields; 16-byte aligned
+ *   actions_out        int64 [m];  logp_out, values_out (component 0), value_targets_out float32 [m]: the columns' rows
+ *   advantages_out     float32 [m]           (advantages[r] - adv_mean) / adv_std: two float32 operations, each rounded, IEEE
+ *                                            division; (0, 1) returns the column unchanged
+ *   seats_out          uint8 [m]             the seat that acted (the record's agent byte)
+ * A row id outside [0, T * num_envs) reads nothing and gives an all-zero output row.  adv_mean must be finite, adv_std finite and
+ * greater than 0.  m == 0 is no work. */
+int skyjo_vec_rollout_gather(skyjo_vec *h, const void *records, int32_t layout, int32_t T, const int64_t *index, int64_t m,
+                             const int32_t *actions, const float *logp, const float *values, int32_t value_stride,
+                             const float *advantages, const float *value_targets, float adv_mean, float adv_std,
+                             float *obs_out, float *logmask_out, int64_t *actions_out, float *logp_out, float *advantages_out,
+                             float *value_targets_out, float *values_out, uint8_t *seats_out, void *stream);
+
 /* host-pointer conveniences for small batches (single-game AEC view): synchronous.  Up to 4096 games they go through
  * host-mapped memory (one launch + one synchronisation per call, no copies), and step_host / reset_host bring every game's
  * state and rewards back with the records: skyjo_vec_get_state and skyjo_vec_get_rewards_host right after them cost no

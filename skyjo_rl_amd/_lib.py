@@ -107,6 +107,9 @@ SIGNATURES = {
     "skyjo_vec_step_collect": (C.c_int, [VP, VP, VP, VP, VP, VP]),
     "skyjo_vec_model_rollout": (C.c_int, [VP, VP, VP, I32, U64, U64, I32, C.POINTER(RolloutBuffers), VP]),
     "skyjo_vec_rollout_targets": (C.c_int, [VP, VP, I32, I32, VP, I32, VP, VP, C.c_float, C.c_float, VP, VP, VP, VP, VP]),
+    "skyjo_vec_rollout_select": (C.c_int, [VP, VP, I64, I32, VP, VP, VP, VP, VP]),
+    "skyjo_vec_rollout_gather": (C.c_int, [VP, VP, I32, I32, VP, I64, VP, VP, VP, I32, VP, VP, C.c_float, C.c_float,
+                                           VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "skyjo_vec_rewards_ptr": (VP, [VP]),
     "skyjo_vec_scores_ptr": (VP, [VP]),
     "skyjo_vec_done_ptr": (VP, [VP]),

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <atomic>
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <string>
@@ -14,6 +15,7 @@
 #include "skyjo_device.h"
 #include "skyjo_policy.h"
 #include "skyjo_targets.h"
+#include "skyjo_batches.h"
 
 // Measurement switches (environment variables: tools/dev/README.md) exist in -DSK_DIAG builds only; the shipped library reads no
 // environment variable at all - what a caller or a test may choose is an option of skyjo_vec_set_option.
@@ -183,6 +185,10 @@ struct skyjo_vec {
   int32_t *d_actions = nullptr;
   uint8_t *d_records = nullptr;
   uint8_t *d_mask = nullptr;
+  // skyjo_vec_rollout_select's scratch (allocated on first use, grown when a call needs more): per block of SK_SEL_ROWS rows its
+  // count / exclusive offset, then the two partial sums.  Not part of a snapshot.
+  void *sel_scratch = nullptr;
+  size_t sel_blocks = 0;
   std::vector<std::pair<void *, size_t>> allocs;  // every device array of the handle with its size (snapshots copy them all)
   // The arrays made at create time are carved out of ONE allocation, the large ones at 2 MB boundaries: how the generator
   // states, the banks and the live tiles lie relative to each other in the memory channels is then the same in every
@@ -743,6 +749,7 @@ int skyjo_vec_destroy(skyjo_vec *h) {
   if (h->ev_scan) (void)hipEventDestroy(h->ev_scan);
   if (h->ev_dealt) (void)hipEventDestroy(h->ev_dealt);
   for (void *p : h->owned) (void)hipFree(p);
+  if (h->sel_scratch) (void)hipFree(h->sel_scratch);
   for (auto &v : h->ev)
     for (auto &e : v) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
   if (h->health_host) (void)hipHostFree(h->health_host);
@@ -1313,6 +1320,73 @@ int skyjo_vec_rollout_targets(skyjo_vec *h, const void *records, int32_t layout,
     case 4: hipLaunchKernelGGL(k_rollout_targets<4>, grid, block, 0, (hipStream_t)stream, a); break;
     default: hipLaunchKernelGGL(k_rollout_targets<0>, grid, block, 0, (hipStream_t)stream, a); break;
   }
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+// ---- learner minibatches of a rollout buffer (include/skyjo_vec.h: skyjo_vec_rollout_select / _gather; the kernels: skyjo_batches.h) ----
+int skyjo_vec_rollout_select(skyjo_vec *h, const uint8_t *flags, int64_t n_rows, int32_t require_bits, const float *advantages,
+                             int64_t *index_out, int64_t *count_out, double *moments_out, void *stream) {
+  if (!h || !flags || !index_out || !count_out) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_select: null argument");
+  if ((advantages == nullptr) != (moments_out == nullptr))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_select: advantages and moments_out go together");
+  if (n_rows < 0 || n_rows > (int64_t)SK_SEL_ROWS * 0x7fffffff) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_select: n_rows out of range");
+  if (require_bits < 1 || require_bits > 255) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_select: require_bits must lie in 1 .. 255");
+  GUARD(h);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t nb = (size_t)((n_rows + SK_SEL_ROWS - 1) / SK_SEL_ROWS);
+  if (!h->sel_scratch || nb > h->sel_blocks) {
+    const size_t cap = nb > 64 ? nb : 64;
+    if (h->sel_scratch) HIPCHK(hipFree(h->sel_scratch));  // (waits for whatever still reads it)
+    h->sel_scratch = nullptr, h->sel_blocks = 0;
+    HIPCHK(hipMalloc(&h->sel_scratch, cap * (sizeof(long long) + 2 * sizeof(double))));
+    h->sel_blocks = cap;
+  }
+  long long *counts = (long long *)h->sel_scratch;
+  double *sums = (double *)(counts + h->sel_blocks);
+  if (nb) {
+    hipLaunchKernelGGL(k_select_pass<false>, dim3((unsigned)nb), dim3(SK_SEL_THREADS), 0, s, flags, (long long)n_rows, (uint32_t)require_bits,
+                       advantages, counts, sums, (long long *)nullptr);
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(SK_SCAN_THREADS), 0, s, counts, (const double *)sums, (int)nb, (long long *)count_out, moments_out);
+  HIPCHK(hipGetLastError());
+  if (nb) {
+    hipLaunchKernelGGL(k_select_pass<true>, dim3((unsigned)nb), dim3(SK_SEL_THREADS), 0, s, flags, (long long)n_rows, (uint32_t)require_bits,
+                       (const float *)nullptr, counts, sums, (long long *)index_out);
+    HIPCHK(hipGetLastError());
+  }
+  return SKYJO_OK;
+}
+
+int skyjo_vec_rollout_gather(skyjo_vec *h, const void *records, int32_t layout, int32_t T, const int64_t *index, int64_t m,
+                             const int32_t *actions, const float *logp, const float *values, int32_t value_stride, const float *advantages,
+                             const float *value_targets, float adv_mean, float adv_std, float *obs_out, float *logmask_out,
+                             int64_t *actions_out, float *logp_out, float *advantages_out, float *value_targets_out, float *values_out,
+                             uint8_t *seats_out, void *stream) {
+  if (!h || !records || !index || !actions || !logp || !values || !advantages || !value_targets || !obs_out || !logmask_out ||
+      !actions_out || !logp_out || !advantages_out || !value_targets_out || !values_out || !seats_out)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather: null argument");
+  if (m < 0 || T < 1 || value_stride < 1) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather: m must not be negative, T and value_stride at least 1");
+  if (layout != SKYJO_REC_ROW_MAJOR && layout != SKYJO_REC_TILE_PLANAR) return fail(SKYJO_E_INVALID, "layout must be SKYJO_REC_ROW_MAJOR or SKYJO_REC_TILE_PLANAR");
+  if (!std::isfinite(adv_mean) || !std::isfinite(adv_std) || !(adv_std > 0.f))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather: adv_mean must be finite, adv_std finite and greater than 0");
+  if ((((uintptr_t)records | (uintptr_t)obs_out | (uintptr_t)logmask_out) & 15) != 0)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather: records, obs_out and logmask_out must be 16-byte aligned");
+  if (m == 0) return SKYJO_OK;
+  GUARD(h);
+  const SkLayout &L = h->P.L;
+  static_assert(SK_GATHER_MAX_PIECES * 16 >= ((19 + 12 * SKYJO_MAX_PLAYERS + 3) & ~3) + 32, "the largest record fits k_gather_rows' LDS image");
+  SkGatherArgs a{};
+  a.rec = (const uint8_t *)records, a.index = (const long long *)index, a.actions = actions, a.logp = logp, a.values = values;
+  a.adv = advantages, a.vt = value_targets;
+  a.obs_out = obs_out, a.lm_out = logmask_out, a.act_out = (long long *)actions_out, a.logp_out = logp_out, a.adv_out = advantages_out;
+  a.vt_out = value_targets_out, a.val_out = values_out, a.seat_out = seats_out;
+  a.planar = layout == SKYJO_REC_TILE_PLANAR;
+  a.m = m, a.n_rows = (long long)T * h->P.B, a.rec_stride = a.planar ? (long long)h->G : (long long)h->P.B;
+  a.B = h->P.B, a.vstride = value_stride, a.rec_bytes = L.rec_bytes, a.D = L.D, a.Dp = L.Dp;
+  a.mean = adv_mean, a.std = adv_std;
+  hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((m + SK_GATHER_ROWS - 1) / SK_GATHER_ROWS)), dim3(SK_GATHER_THREADS), 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return SKYJO_OK;
 }

@@ -8,9 +8,13 @@ between them.  ``collect_stepwise`` is the same loop made one launch at a time f
 records), action, log-probability, value estimate, the acting agent, done flags and - at episode ends - the final rewards of
 skyjo_env.py:293-312 for every seat.  ``RolloutBuffer.valid`` tells a learner which rows are transitions at all.  ``compute_targets`` adds what RLlib's PPO attaches to those
 batches - ``advantages`` and ``value_targets`` by GAE per agent trajectory - in one more native call on the buffer as it lies
-(``skyjo_vec_rollout_targets``).
+(``skyjo_vec_rollout_targets``).  ``select_rows`` / ``gather_rows`` / ``minibatches`` hand the buffer to a learner: the rows that
+carry a target, the moments of their advantages, and shuffled minibatches as dense float tensors - again on the buffer as it lies
+(``skyjo_vec_rollout_select`` / ``_gather``): no row-major copy of a tile-planar buffer, no knowledge of the record layout.
 """
 import ctypes as C
+import math
+from collections import namedtuple
 
 import torch
 
@@ -105,3 +109,97 @@ def compute_targets(buf, gamma=0.99, lam=1.0):
                                            float(gamma), float(lam), vp(buf.advantages), vp(buf.value_targets), vp(buf.returns),
                                            vp(buf.target_flags), buf._env._stream()))
     return buf
+
+
+Selection = namedtuple("Selection", ["index", "count", "mean", "std"])
+Minibatch = namedtuple("Minibatch", ["observations", "log_mask", "actions", "logp", "advantages", "value_targets", "values", "seats"])
+
+
+def _check_records(buf):
+    """``buf.planar`` must describe ``buf.records``: [T + 1, tiles, P, 64, 16] tile-planar, [T + 1, B, record_bytes] row-major."""
+    e, r = buf._env, buf.records
+    want = (buf.T + 1, e.tiles, e.record_bytes // 16, 64, 16) if buf.planar else (buf.T + 1, buf.B, e.record_bytes)
+    if tuple(r.shape) != want or not r.is_contiguous():
+        raise ValueError(f"buf.records has shape {tuple(r.shape)}, but planar={buf.planar} means {want}")
+
+
+@torch.no_grad()
+def select_rows(buf, require=_lib.TGT_HAS_TARGET):
+    """The rows of a buffer whose ``target_flags`` have every bit of ``require`` (``compute_targets`` must have run), in one native
+    call (``skyjo_vec_rollout_select``): ``Selection(index, count, mean, std)`` - ``index`` int64 [count], ascending row ids
+    ``t * B + b`` (what ``torch.nonzero`` gives; a view of ``buf.row_index``, int64 [T * B], allocated once and refilled by every
+    call), ``mean`` / ``std`` Python floats: the moments of the selected rows' ``advantages``, computed in double from the two sums
+    the kernel returns, ``std`` unbiased like ``torch.std`` (0.0 for fewer than two rows).  Reading back the count (with the sums,
+    one copy) is the only synchronisation."""
+    if getattr(buf, "target_flags", None) is None:
+        raise ValueError("select_rows needs the columns of compute_targets(buf)")
+    _check_records(buf)
+    L = _lib.load()
+    n = buf.T * buf.B
+    if getattr(buf, "row_index", None) is None:
+        dev = buf.actions.device
+        buf.row_index = torch.empty((n,), dtype=torch.int64, device=dev)
+        buf._select_out = torch.empty((3,), dtype=torch.int64, device=dev)  # the count, then the two sums (as doubles)
+    out = buf._select_out
+    _lib.check(L.skyjo_vec_rollout_select(buf._env._h, buf.target_flags.data_ptr(), n, int(require), buf.advantages.data_ptr(),
+                                          buf.row_index.data_ptr(), out.data_ptr(), out[1:].data_ptr(), buf._env._stream()))
+    host = out.cpu()
+    count = int(host[0])
+    s, q = (float(x) for x in host[1:].view(torch.float64))
+    mean = s / count if count else 0.0
+    std = math.sqrt(max(q - s * s / count, 0.0) / (count - 1)) if count > 1 else 0.0
+    return Selection(buf.row_index[:count], count, mean, std)
+
+
+def new_minibatch(buf, size):
+    """An empty ``Minibatch`` of ``size`` rows for ``gather_rows(..., out=)``."""
+    dev, f = buf.actions.device, torch.float32
+    e = lambda *shape, dtype=f: torch.empty(shape, dtype=dtype, device=dev)
+    return Minibatch(e(size, buf._env.obs_dim), e(size, 26), e(size, dtype=torch.int64), e(size), e(size), e(size), e(size),
+                     e(size, dtype=torch.uint8))
+
+
+@torch.no_grad()
+def gather_rows(buf, index, normalize=None, out=None):
+    """The rows ``index`` (int64 row ids ``t * B + b`` on the buffer's device, any order, repeats allowed) as a ``Minibatch`` of
+    dense tensors, one native call (``skyjo_vec_rollout_gather``) on the buffer as it lies: ``observations`` float32 [m, D],
+    ``log_mask`` float32 [m, 26] (0 where the action is legal, ``FLOAT_MIN`` where not: add it to the logits), ``actions`` int64,
+    ``logp`` / ``advantages`` / ``value_targets`` / ``values`` float32 and ``seats`` uint8 [m].  ``normalize``: ``(mean, std)`` -
+    advantages come as ``(a - mean) / std`` in float32 - or None, which leaves them as they are.  ``out``: a ``Minibatch`` of at
+    least m rows to refill (``new_minibatch``); its first m rows are returned.  A row id outside [0, T * B) gives a row of zeros."""
+    if getattr(buf, "advantages", None) is None:
+        raise ValueError("gather_rows needs the columns of compute_targets(buf)")
+    _check_records(buf)
+    if index.dtype != torch.int64 or index.dim() != 1 or index.device != buf.actions.device:
+        raise ValueError("index must be a one-dimensional int64 tensor on the buffer's device")
+    index = index.contiguous()
+    m = index.numel()
+    mean, std = (0.0, 1.0) if normalize is None else normalize
+    if out is None:
+        out = new_minibatch(buf, m)
+    elif any(c.shape[0] < m or not c.is_contiguous() for c in out):
+        raise ValueError("out holds fewer rows than index")
+    L = _lib.load()
+    vp = lambda t: t.data_ptr()
+    _lib.check(L.skyjo_vec_rollout_gather(buf._env._h, vp(buf.records), _lib.REC_TILE_PLANAR if buf.planar else _lib.REC_ROW_MAJOR, buf.T,
+                                          vp(index), m, vp(buf.actions), vp(buf.logp), vp(buf.values), buf.values.shape[-1],
+                                          vp(buf.advantages), vp(buf.value_targets), float(mean), float(std), vp(out.observations),
+                                          vp(out.log_mask), vp(out.actions), vp(out.logp), vp(out.advantages), vp(out.value_targets),
+                                          vp(out.values), vp(out.seats), buf._env._stream()))
+    return out if out.actions.shape[0] == m else Minibatch(*(c[:m] for c in out))
+
+
+def minibatches(buf, size, generator=None, normalize=True, require=_lib.TGT_HAS_TARGET, selection=None):
+    """One epoch over the selected rows in shuffled minibatches: ``select_rows`` (or a ``selection`` made earlier), a
+    ``torch.randperm`` of it (``generator``: a generator on the buffer's device), and ``gather_rows`` per slice of ``size`` rows into
+    ONE ``Minibatch`` that every step refills - use a batch before asking for the next.  The last slice may be short.
+    ``normalize``: True - the selection's (mean, std), a std of 0 counting as 1; ``(mean, std)``; or None / False."""
+    sel = select_rows(buf, require) if selection is None else selection
+    if normalize is True:
+        normalize = (sel.mean, sel.std if sel.std > 0.0 else 1.0)
+    elif normalize is False:
+        normalize = None
+    perm = sel.index[torch.randperm(sel.count, device=sel.index.device, generator=generator)]
+    out = new_minibatch(buf, min(size, sel.count))
+    for k in range(0, sel.count, size):
+        yield gather_rows(buf, perm[k:k + size], normalize=normalize, out=out)

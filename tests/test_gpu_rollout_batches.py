@@ -1,0 +1,363 @@
+"""``rollout.select_rows`` / ``gather_rows`` / ``minibatches`` (``skyjo_vec_rollout_select`` / ``_gather``: a filled buffer as learner
+minibatches, on the buffer as it lies): the selection against ``torch.nonzero`` and its moments against float64 sums, the gather
+bit for bit against the numpy restatement of tests/rollout_batches_ref.py in either record layout and for the record sizes whose mask
+and meta bytes straddle 16-byte pieces, rows out of range, the argument errors, and a PPO update on native minibatches."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+NAMES = ("observations", "log_mask", "actions", "logp", "advantages", "value_targets", "values", "seats")
+
+
+def _rollout(B, N, T, layout="row-major", seed=9, model_seed=0):
+    import torch
+
+    from skyjo_rl_amd import SkyjoVecEnv
+    from skyjo_rl_amd.action_mask_model import ActionMaskModel, FusedNet
+    from skyjo_rl_amd.rollout import RolloutBuffer, collect, compute_targets
+
+    torch.manual_seed(model_seed)
+    env = SkyjoVecEnv(B, num_players=N)
+    env.set_record_layout(layout)
+    env.seed(None, seed)
+    env.reset()
+    model = ActionMaskModel(obs_dim=env.obs_dim).cuda()
+    pol, val = FusedNet(model.policy), FusedNet(model.value)
+    buf = RolloutBuffer(env, T)
+    collect(env, pol, val, buf, seed=1, first_ticket=0)
+    compute_targets(buf, gamma=0.99, lam=0.95)
+    return env, model, (pol, val), buf
+
+
+def _close(env, nets):
+    for n in nets:
+        n.close()
+    env.close()
+
+
+def _restate(buf, index, normalize=None):
+    """The restatement's Minibatch for a buffer, from its raw record bytes in the buffer's own layout."""
+    from tests import rollout_batches_ref as ref
+
+    e = buf._env
+    mean, std = normalize or (0.0, 1.0)
+    return ref.gather(buf.records.cpu().numpy(), buf.planar, e.record_bytes, e.obs_dim, buf.B, buf.T, e.tiles * 64 if buf.planar else buf.B,
+                      index.cpu().numpy(), buf.actions.cpu().numpy(), buf.logp.cpu().numpy(), buf.values[..., 0].cpu().numpy(),
+                      buf.advantages.cpu().numpy(), buf.value_targets.cpu().numpy(), mean, std)
+
+
+def _assert_minibatch(mb, want, what):
+    import torch
+
+    for name, got in zip(NAMES, mb):
+        w = torch.from_numpy(want[name])
+        assert got.dtype == w.dtype and tuple(got.shape) == tuple(w.shape), (what, name, got.dtype, got.shape)
+        assert torch.equal(got.cpu(), w), (what, name)
+
+
+def _native_select(L, env, flags, require, adv):
+    import torch
+
+    n = flags.numel()
+    index = torch.full((max(n, 1),), -7, dtype=torch.int64, device="cuda")
+    out = torch.full((3,), -1, dtype=torch.int64, device="cuda")
+    rc = L.skyjo_vec_rollout_select(env._h, flags.data_ptr(), n, require, adv.data_ptr() if adv is not None else None, index.data_ptr(),
+                                    out.data_ptr(), out[1:].data_ptr() if adv is not None else None, env._stream())
+    assert rc == 0
+    return index, int(out[0]), out[1:].view(torch.float64).cpu().numpy().copy()
+
+
+@pytest.fixture(scope="module")
+def small_env():
+    from skyjo_rl_amd import SkyjoVecEnv
+
+    env = SkyjoVecEnv(64)
+    yield env
+    env.close()
+
+
+SELECT_CASES = [(1, "random"), (63, "random"), (64, "random"), (65, "random"), (4095, "random"), (4097, "random"), (4097, "zeros"),
+                (4097, "threes"), (1000003, "random")]
+
+
+@pytest.mark.parametrize("n,kind", SELECT_CASES)
+def test_select_on_synthetic_flags(small_env, n, kind):
+    """Index and count are ``torch.nonzero``'s; the two sums lie within 2 n 2^-53 sum|x| of numpy's float64 sums (either order of
+    summation is within (n - 1) 2^-53 sum|x| of the exact sum to first order); a second call gives the same bits."""
+    import torch
+
+    from skyjo_rl_amd import _lib
+
+    L = _lib.load()
+    g = torch.Generator().manual_seed(n)
+    flags = {"random": torch.randint(0, 4, (n,), dtype=torch.uint8, generator=g), "zeros": torch.zeros(n, dtype=torch.uint8),
+             "threes": torch.full((n,), 3, dtype=torch.uint8)}[kind].cuda()
+    adv = (torch.randn(n, generator=g) * 25.0).cuda()
+    a64 = adv.cpu().numpy().astype(np.float64)
+    for require in (1, 2, 3):
+        index, count, mom = _native_select(L, small_env, flags, require, adv)
+        want = ((flags & require) == require).nonzero().squeeze(1)
+        assert count == want.numel() and torch.equal(index[:count], want), (n, kind, require)
+        x = a64[want.cpu().numpy()]
+        for got, ref_sum, mag in ((mom[0], x.sum(), np.abs(x).sum()), (mom[1], (x * x).sum(), (x * x).sum())):
+            bound = 2 * count * 2.0 ** -53 * mag
+            print(f"n={n} {kind} require={require}: count={count} sum={got!r} numpy={ref_sum!r} |diff|={abs(got - ref_sum):.3e} bound={bound:.3e}")
+            assert abs(got - ref_sum) <= bound
+        if count == 0:
+            assert mom.tolist() == [0.0, 0.0]
+        index2, count2, mom2 = _native_select(L, small_env, flags, require, adv)
+        assert count2 == count and torch.equal(index2[:count], index[:count]) and mom2.tobytes() == mom.tobytes()
+    # without advantages: the same list, no moments
+    index3, count3, _ = _native_select(L, small_env, flags, 1, None)
+    want = (flags & 1).nonzero().squeeze(1)
+    assert count3 == want.numel() and torch.equal(index3[:count3], want)
+
+
+@pytest.fixture(scope="module")
+def buffers_200():
+    """B = 200 (three tiles and a partial one), N = 3, T = 48 in both layouts: the same rollout twice."""
+    made = {}
+    for layout in ("row-major", "tile-planar-all"):
+        made[layout] = _rollout(200, 3, 48, layout=layout)
+    yield {k: v[3] for k, v in made.items()}
+    for env, _, nets, _ in made.values():
+        _close(env, nets)
+
+
+def _index_lists(sel):
+    import torch
+
+    g = torch.Generator().manual_seed(11)
+    perm = sel.index[torch.randperm(sel.count, generator=g).cuda()]
+    rep = torch.cat([perm[:70], perm[:70].flip(0), perm[5:6].repeat(9)])
+    lists = {"ascending": sel.index, "permuted": perm, "repeats": rep}
+    for m in (1, 63, 65):
+        lists[f"m={m}"] = perm[:m].contiguous()
+    return lists
+
+
+def test_gather_bitwise_on_real_buffers(buffers_200):
+    import torch
+
+    from skyjo_rl_amd.action_mask_model import FLOAT_MIN
+    from skyjo_rl_amd.rollout import gather_rows, select_rows
+
+    result = {}
+    for layout, buf in buffers_200.items():
+        assert buf.planar == (layout != "row-major")
+        sel = select_rows(buf)
+        want_index = (buf.target_flags.reshape(-1) & 1).nonzero().squeeze(1)
+        assert sel.count == want_index.numel() > 1000 and torch.equal(sel.index, want_index)
+        assert sel.index.data_ptr() == buf.row_index.data_ptr() and buf.row_index.numel() == buf.T * buf.B
+        v = buf.views()
+        obs_all = v.observations[:buf.T].reshape(-1, v.observations.shape[-1])
+        mask_all = v.action_mask[:buf.T].reshape(-1, 26)
+        for what, index in _index_lists(sel).items():
+            for norm in (None, (sel.mean, sel.std)):
+                mb = gather_rows(buf, index, normalize=norm)
+                _assert_minibatch(mb, _restate(buf, index, norm), (layout, what, norm))
+                result[(layout, what, norm is None)] = [c.clone() for c in mb]
+            assert torch.equal(mb.observations, obs_all[index].to(torch.float32))
+            assert torch.equal(mb.log_mask, torch.clamp(torch.log(mask_all[index].to(torch.float32)), min=FLOAT_MIN))
+            assert torch.equal(mb.seats, v.agent[:buf.T].reshape(-1)[index])
+        # `out` is refilled in place and a shorter list returns its first rows
+        out = gather_rows(buf, sel.index[:65])
+        again = gather_rows(buf, sel.index[3:40], out=out)
+        assert again.actions.data_ptr() == out.actions.data_ptr() and again.observations.shape[0] == 37
+        _assert_minibatch(again, _restate(buf, sel.index[3:40]), (layout, "out"))
+    for (layout, what, plain), cols in result.items():
+        if layout == "row-major":
+            for a, b in zip(cols, result[("tile-planar-all", what, plain)]):
+                assert torch.equal(a, b), (what, plain)
+
+
+@pytest.mark.parametrize("N", [4, 12])
+def test_record_sizes_that_straddle_pieces(N):
+    """Direct observation: the mask offset (68 / 164) is no multiple of 16, so the mask and the meta bytes cross 16-byte pieces.
+    Row-major records from the engine, the same records re-laid tile-planar by the test helper; both through the C ABI."""
+    import torch
+
+    from skyjo_rl_amd import SkyjoVecEnv, _lib
+    from tests import rollout_batches_ref as ref
+
+    B, T = 104, 16
+    env = SkyjoVecEnv(B, num_players=N, observe_other_player_indirect=False)
+    assert env.record_bytes == {4: 112, 12: 208}[N] and env.mask_offset % 16 != 0
+    env.seed(None, 30 + N)
+    rows = env.new_records(T)
+    env.rollout(T, policy_seed=3, records=rows, actions=torch.empty((T, B), dtype=torch.int32, device="cuda"))
+    rows_np = rows.cpu().numpy()
+    planar_np = ref.to_planar(rows_np)
+    planar = torch.from_numpy(planar_np).cuda()
+    g = torch.Generator().manual_seed(N)
+    n = T * B
+    cols = dict(actions=torch.randint(0, 26, (n,), dtype=torch.int32, generator=g), logp=-torch.rand(n, generator=g),
+                values=torch.randn(n, generator=g), advantages=torch.randn(n, generator=g) * 9, value_targets=torch.randn(n, generator=g))
+    dev = {k: v.cuda() for k, v in cols.items()}
+    index = torch.cat([torch.randperm(n, generator=g)[:n - 7], torch.tensor([0, n - 1, 5, 5])]).cuda()
+    m = index.numel()
+    L = _lib.load()
+    mean, std = 0.25, 1.75
+    want = None
+    for layout, rec, rec_np, stride in ((_lib.REC_ROW_MAJOR, rows, rows_np, B), (_lib.REC_TILE_PLANAR, planar, planar_np, planar_np.shape[1] * 64)):
+        out = (torch.empty((m, env.obs_dim), device="cuda"), torch.empty((m, 26), device="cuda"), torch.empty(m, dtype=torch.int64, device="cuda"),
+               torch.empty(m, device="cuda"), torch.empty(m, device="cuda"), torch.empty(m, device="cuda"), torch.empty(m, device="cuda"),
+               torch.empty(m, dtype=torch.uint8, device="cuda"))
+        obs, lm, act, logp, adv, vt, val, seats = out
+        rc = L.skyjo_vec_rollout_gather(env._h, rec.data_ptr(), layout, T, index.data_ptr(), m, dev["actions"].data_ptr(), dev["logp"].data_ptr(),
+                                        dev["values"].data_ptr(), 1, dev["advantages"].data_ptr(), dev["value_targets"].data_ptr(), mean, std,
+                                        obs.data_ptr(), lm.data_ptr(), act.data_ptr(), logp.data_ptr(), adv.data_ptr(), vt.data_ptr(),
+                                        val.data_ptr(), seats.data_ptr(), env._stream())
+        assert rc == 0
+        want = ref.gather(rec_np, layout == _lib.REC_TILE_PLANAR, env.record_bytes, env.obs_dim, B, T, stride, index.cpu().numpy(),
+                          **{k: v.numpy() for k, v in cols.items()}, mean=mean, std=std)
+        _assert_minibatch(out, want, (N, layout))
+    # the sample exercises what it is about: legal and illegal actions, more than one seat, both card signs
+    assert (want["log_mask"] == 0).any() and (want["log_mask"] != 0).any() and len(set(want["seats"].tolist())) > 1
+    assert (want["observations"] < 0).any() and (want["observations"] > 0).any()
+    env.close()
+
+
+@pytest.mark.parametrize("N", [1, 2, 5, 8])
+def test_player_counts_bitwise(N):
+    import torch
+
+    from skyjo_rl_amd.rollout import gather_rows, select_rows
+
+    env, _, nets, buf = _rollout(128, N, 32, seed=40 + N)
+    sel = select_rows(buf)
+    want = (buf.target_flags.reshape(-1) & 1).nonzero().squeeze(1)
+    assert sel.count == want.numel() > 0 and torch.equal(sel.index, want)
+    g = torch.Generator().manual_seed(N)
+    index = sel.index[torch.randperm(sel.count, generator=g).cuda()]
+    norm = (sel.mean, sel.std)
+    _assert_minibatch(gather_rows(buf, index, normalize=norm), _restate(buf, index, norm), N)
+    assert int(gather_rows(buf, index).seats.max()) == N - 1
+    _close(env, nets)
+
+
+@pytest.mark.parametrize("layout", ["row-major", "tile-planar-all"])
+def test_selection_spans_many_blocks(layout):
+    """B = 4 096 + 40, T = 160: 162 blocks of 4 096 rows, the last one partial."""
+    import torch
+
+    from skyjo_rl_amd.rollout import gather_rows, minibatches, select_rows
+
+    env, _, nets, buf = _rollout(4096 + 40, 3, 160, layout=layout)
+    sel = select_rows(buf)
+    mask = (buf.target_flags & 1) != 0
+    want = mask.reshape(-1).nonzero().squeeze(1)
+    assert sel.count == want.numel() and torch.equal(sel.index, want)
+    a = buf.advantages[mask].double()
+    mean, std = float(a.mean()), float(a.std())
+    print(f"{layout}: count={sel.count} mean={sel.mean!r} torch={mean!r} std={sel.std!r} torch={std!r}")
+    assert abs(sel.mean - mean) <= 1e-12 * abs(mean) and abs(sel.std - std) <= 1e-12 * abs(std)
+    # one epoch: the generator reproduces the permutation, every slice is the gather of its rows, the slices tile the selection
+    size = 32768
+    dev = buf.actions.device
+    gen = torch.Generator(device=dev).manual_seed(5)
+    perm = sel.index[torch.randperm(sel.count, device=dev, generator=torch.Generator(device=dev).manual_seed(5))]
+    seen, k = [], 0
+    for mb in minibatches(buf, size, generator=gen, normalize=True):
+        rows = perm[k:k + size]
+        assert mb.actions.numel() == rows.numel()
+        one = gather_rows(buf, rows, normalize=(sel.mean, sel.std))
+        assert all(torch.equal(x, y) for x, y in zip(mb, one))
+        seen.append(rows)
+        k += size
+    assert len(seen) == (sel.count + size - 1) // size and seen[-1].numel() == sel.count - (len(seen) - 1) * size
+    assert torch.equal(torch.cat(seen).sort().values, sel.index)
+    _close(env, nets)
+
+
+def test_rows_out_of_range(buffers_200):
+    import torch
+
+    from skyjo_rl_amd.rollout import gather_rows
+
+    for buf in buffers_200.values():
+        n = buf.T * buf.B
+        mb = gather_rows(buf, torch.tensor([n, -1, 0], dtype=torch.int64, device="cuda"), normalize=(0.5, 2.0))
+        for c in mb:
+            assert not c[:2].any()
+        first = gather_rows(buf, torch.tensor([0], dtype=torch.int64, device="cuda"), normalize=(0.5, 2.0))
+        assert all(torch.equal(c[2:], d) for c, d in zip(mb, first)) and bool(first.log_mask.any()) and bool(first.observations.any())
+
+
+def test_argument_errors(buffers_200):
+    import torch
+
+    from skyjo_rl_amd import _lib
+    from skyjo_rl_amd.rollout import gather_rows, new_minibatch, select_rows
+
+    buf = buffers_200["row-major"]
+    env = buf._env
+    L = _lib.load()
+    p = lambda t: t.data_ptr()
+    n = buf.T * buf.B
+    flags, index = buf.target_flags, torch.empty(n, dtype=torch.int64, device="cuda")
+    out = torch.zeros(3, dtype=torch.int64, device="cuda")
+    good = [env._h, p(flags), n, 1, p(buf.advantages), p(index), p(out), p(out[1:]), env._stream()]
+    assert L.skyjo_vec_rollout_select(*good) == 0
+    bad = [good[:k] + [None] + good[k + 1:] for k in (0, 1, 5, 6)]        # every required pointer
+    bad += [good[:4] + [None] + good[5:], good[:7] + [None] + good[8:]]   # advantages and moments go together
+    bad += [good[:3] + [x] + good[4:] for x in (0, 256, -1)] + [good[:2] + [-1] + good[3:]]
+    for args in bad:
+        assert L.skyjo_vec_rollout_select(*args) == -1, args
+    out.fill_(-1)
+    assert L.skyjo_vec_rollout_select(*(good[:2] + [0] + good[3:])) == 0                 # no rows: count 0, zero moments
+    assert out.cpu().tolist() == [0, 0, 0]
+    assert L.skyjo_vec_rollout_select(*(good[:4] + [None] + good[5:7] + [None] + good[8:])) == 0
+
+    mb = new_minibatch(buf, 8)
+    idx = select_rows(buf).index[:8].contiguous()
+    good = [env._h, p(buf.records), _lib.REC_ROW_MAJOR, buf.T, p(idx), 8, p(buf.actions), p(buf.logp), p(buf.values), 1, p(buf.advantages),
+            p(buf.value_targets), 0.0, 1.0, p(mb.observations), p(mb.log_mask), p(mb.actions), p(mb.logp), p(mb.advantages), p(mb.value_targets),
+            p(mb.values), p(mb.seats), env._stream()]
+    assert L.skyjo_vec_rollout_gather(*good) == 0
+    sub = lambda k, x: good[:k] + [x] + good[k + 1:]
+    bad = [sub(k, None) for k in (0, 1, 4, 6, 7, 8, 10, 11, 14, 15, 16, 17, 18, 19, 20, 21)]   # every pointer
+    bad += [sub(13, x) for x in (0.0, float("nan"), -1.0, float("inf"))] + [sub(12, float("nan")), sub(12, float("inf"))]
+    bad += [sub(3, 0), sub(2, 7), sub(5, -1), sub(9, 0)]
+    for args in bad:
+        assert L.skyjo_vec_rollout_gather(*args) == -1, args
+    assert L.skyjo_vec_rollout_gather(*sub(5, 0)) == 0
+    with pytest.raises(_lib.SkyjoNativeError):
+        gather_rows(buf, idx, normalize=(0.0, 0.0))
+    with pytest.raises(ValueError):
+        gather_rows(buf, idx.to(torch.int32))
+    planar = buffers_200["tile-planar-all"]
+    planar.planar = False                      # the flag must describe the records
+    try:
+        with pytest.raises(ValueError):
+            gather_rows(planar, idx)
+        with pytest.raises(ValueError):
+            select_rows(planar)
+    finally:
+        planar.planar = True
+
+
+def test_ppo_update_on_native_batches(monkeypatch):
+    """``ppo_update(..., gae=(0.99, 0.95), native_batches=True)`` at 4 096 x 3, T = 320, three epochs: learns, and never asks for
+    ``buf.views()``."""
+    import torch
+
+    from examples.ppo import ppo_update
+    from skyjo_rl_amd.rollout import RolloutBuffer
+
+    env, model, nets, buf = _rollout(4096, 3, 320)
+    opt = torch.optim.Adam(model.parameters(), lr=3e-4)
+
+    def no_views(self, env=None):
+        raise AssertionError("native_batches=True must not call buf.views()")
+
+    monkeypatch.setattr(RolloutBuffer, "views", no_views)
+    out = ppo_update(model, buf, opt, epochs=3, gae=(0.99, 0.95), native_batches=True)
+    monkeypatch.undo()
+    assert out["transitions"] == int((buf.target_flags & 1).sum()) > 0
+    assert all(torch.isfinite(torch.tensor([out[k][j] for k in ("first", "last") for j in ("policy_loss", "vf_loss", "kl")])))
+    assert out["last"]["vf_loss"] < out["first"]["vf_loss"]
+    with pytest.raises(ValueError):
+        ppo_update(model, buf, opt, native_batches=True)
+    _close(env, nets)
