@@ -65,6 +65,7 @@ def _native_select(L, env, flags, require, adv):
     rc = L.skyjo_vec_rollout_select(env._h, flags.data_ptr(), n, require, adv.data_ptr() if adv is not None else None, index.data_ptr(),
                                     out.data_ptr(), out[1:].data_ptr() if adv is not None else None, env._stream())
     assert rc == 0
+    assert bool((index[int(out[0]):] == -7).all())   # only the first count entries are written
     return index, int(out[0]), out[1:].view(torch.float64).cpu().numpy().copy()
 
 
