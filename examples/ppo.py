@@ -12,6 +12,7 @@ import torch
 
 from skyjo_rl_amd._lib import TGT_HAS_TARGET
 from skyjo_rl_amd.action_mask_model import FLOAT_MIN, FusedNet
+from skyjo_rl_amd.learner import STATS, PPOLossBuffers, ppo_loss
 from skyjo_rl_amd.rollout import compute_targets, minibatches, select_rows
 
 
@@ -65,13 +66,53 @@ def _ppo_update_native(model, buf, optimizer, epochs, minibatch, clip, vf_coef, 
     return {"first": stats[0], "last": stats[-1], "transitions": sel.count}
 
 
-def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_coef=1.0, seed=0, gae=None, native_batches=False):
+def _ppo_update_native_loss(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip):
+    """``ppo_update(..., native_batches=True, native_loss=True)``: the minibatches AND the loss head in native calls
+    (``learner.ppo_loss``: loss, statistics and the gradients with respect to the model's two outputs in one kernel); autograd runs
+    through the two branches only, and the statistics stay on the device until the epoch is over - one read per epoch."""
+    compute_targets(buf, gamma=gae[0], lam=gae[1])
+    sel = select_rows(buf, TGT_HAS_TARGET)
+    norm = (sel.mean, max(sel.std, 1e-6))
+    gen = torch.Generator(device=buf.actions.device).manual_seed(seed)
+    out = PPOLossBuffers(max(min(minibatch, sel.count), 1), buf.actions.device)
+    stats = []
+    for ep in range(epochs):
+        tot = torch.zeros((6,), dtype=torch.float64, device=buf.actions.device)
+        rows = 0
+        for mb in minibatches(buf, minibatch, generator=gen, normalize=norm, selection=sel):
+            logits = model.policy(mb.observations)  # (the kernel adds the mask: action_mask_model.py:70-71)
+            value = model.value(mb.observations)
+            res = ppo_loss(logits, value, mb, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, vf_clip=vf_clip, out=out)
+            optimizer.zero_grad(set_to_none=True)
+            torch.autograd.backward([logits, value], [res.grad_logits, res.grad_value])
+            optimizer.step()
+            n = mb.actions.numel()
+            tot += res.stats * n
+            rows += n
+        host = (tot / max(rows, 1)).tolist()  # the epoch's one read
+        stats.append({k: host[STATS.index(k)] for k in ("policy_loss", "vf_loss", "kl", "entropy", "clip_fraction")})
+    return {"first": stats[0], "last": stats[-1], "transitions": sel.count}
+
+
+def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_coef=1.0, seed=0, gae=None, native_batches=False,
+               native_loss=False, ent_coef=0.0, vf_clip=None):
     """Clipped-surrogate PPO epochs over the buffer (RLlib defaults: clip_param 0.3, vf_loss_coeff 1.0).  Returns the mean
     losses of the first and the last epoch.  ``gae``: None - Monte-Carlo returns of the episodes that ended inside the buffer
     (``compute_returns``); (gamma, lambda) - advantages, value targets and the row mask of ``rollout.compute_targets`` (one
     native call; rows of unfinished episodes take part, bootstrapped from the value estimates).  ``native_batches`` (needs
     ``gae``): the minibatches come from ``rollout.minibatches`` - row selection, advantage moments and the gather in native calls
-    on the buffer as it lies, no ``buf.views()`` - instead of the torch expressions below."""
+    on the buffer as it lies, no ``buf.views()`` - instead of the torch expressions below.  ``native_loss`` (needs
+    ``native_batches``): the loss head is ``learner.ppo_loss`` - one kernel between the model's outputs and ``optimizer.step()``; only
+    this path knows ``ent_coef`` (an entropy bonus) and ``vf_clip`` (RLlib's ``vf_clip_param``), and its statistics gain ``entropy``
+    and ``clip_fraction``."""
+    if native_loss:
+        if not native_batches:
+            raise ValueError("native_loss=True needs native_batches=True")
+        if gae is None:
+            raise ValueError("native_batches=True needs gae=(gamma, lambda)")
+        return _ppo_update_native_loss(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip)
+    if ent_coef != 0.0 or vf_clip is not None:
+        raise ValueError("ent_coef and vf_clip belong to native_loss=True")
     if native_batches:
         if gae is None:
             raise ValueError("native_batches=True needs gae=(gamma, lambda)")

@@ -464,6 +464,37 @@ int skyjo_vec_rollout_gather(skyjo_vec *h, const void *records, int32_t layout, 
                              float *obs_out, float *logmask_out, int64_t *actions_out, float *logp_out, float *advantages_out,
                              float *value_targets_out, float *values_out, uint8_t *seats_out, void *stream);
 
+/* The PPO loss head of a learner minibatch, on device: everything between a model's two outputs and optimizer.step() - the masked
+ * softmax of action_mask_model.py:58-74, the clipped surrogate, the value loss and the entropy of the PPO the reference trains with
+ * (rlskyjo/models/train_model_simple_rllib.py:54-57) - in one kernel that reads every input once and writes the gradients with
+ * respect to the logits and the value, plus a single-workgroup launch that finishes the statistics.  Needs no engine handle: it runs
+ * on the current device, on `stream`.  All arrays are dense device arrays of m >= 1 rows:
+ *   logits         float32 [m][26]  the policy branch's raw output; 16-byte aligned
+ *   log_mask       float32 [m][26]  logmask_out of skyjo_vec_rollout_gather (0 or -FLT_MAX); 16-byte aligned
+ *   value          float32 [m];  actions int64 [m], each in [0, 26) - a precondition: an action outside is read as action 0
+ *   logp_old, advantages, value_targets, values_old  float32 [m]
+ *   clip > 0 (finite);  vf_coef;  ent_coef;  vf_clip: <= 0, +inf or NaN mean "no value clipping"
+ * Per row, in float32:  z = logits + log_mask;  M = max z;  e = exp(z - M);  S = sum e;  logp = z - M - log S;  p = e / S (a masked
+ * action has p == 0 exactly);  lp = logp[action];  r = exp(lp - logp_old);  A = advantage;
+ *   pl = -min(r A, clamp(r, 1 - clip, 1 + clip) A);   H = -sum over p > 0 of p logp;   kl = logp_old - lp;
+ *   vl = (v - vt)^2, and with value clipping vl = max(vl, (vc - vt)^2), vc = v_old + clamp(v - v_old, -vf_clip, vf_clip);
+ *   clipped = (A > 0 and r > 1 + clip) or (A < 0 and r < 1 - clip).
+ * L = 1/m sum (pl + vf_coef vl - ent_coef H).  The outputs:
+ *   grad_logits_out float32 [m][26] dL/dlogits = 1/m [ -g r (delta_ka - p_k) + ent_coef p_k (logp_k + H) ], g = 0 if clipped else A; the
+ *                                   entropy term is exactly 0 where p_k == 0, so a masked k != action gets exactly 0.0; 16-byte aligned
+ *   grad_value_out  float32 [m]     1/m vf_coef d, d = 2 (v - vt) - but 0 where the value clamp saturates and (vc - vt)^2 > (v - vt)^2
+ *   stats_out       double [6]      loss, policy_loss, vf_loss, entropy, kl, clip_fraction: means over the m rows; every row's terms are
+ *                                   widened to double first and summed in a fixed order without atomics - the same input gives the
+ *                                   same bits on every call
+ *   scratch         caller-owned, 8-byte aligned, at least skyjo_vec_ppo_loss_scratch_bytes(m) bytes (the per-workgroup partial sums)
+ * These are the gradients torch's autograd gives for the same expression.  SKYJO_E_INVALID on a null pointer, m < 1, a clip that is
+ * not finite and positive, a misaligned array or a scratch that is too small. */
+int64_t skyjo_vec_ppo_loss_scratch_bytes(int64_t m); /* 0 for m < 1 */
+int skyjo_vec_ppo_loss(const float *logits, const float *log_mask, const float *value, const int64_t *actions, const float *logp_old,
+                       const float *advantages, const float *value_targets, const float *values_old, int64_t m, float clip,
+                       float vf_coef, float ent_coef, float vf_clip, float *grad_logits_out, float *grad_value_out,
+                       double *stats_out /* device, 6 */, void *scratch, int64_t scratch_bytes, void *stream);
+
 /* host-pointer conveniences for small batches (single-game AEC view): synchronous.  Up to 4096 games they go through
  * host-mapped memory (one launch + one synchronisation per call, no copies), and step_host / reset_host bring every game's
  * state and rewards back with the records: skyjo_vec_get_state and skyjo_vec_get_rewards_host right after them cost no

@@ -110,6 +110,9 @@ SIGNATURES = {
     "skyjo_vec_rollout_select": (C.c_int, [VP, VP, I64, I32, VP, VP, VP, VP, VP]),
     "skyjo_vec_rollout_gather": (C.c_int, [VP, VP, I32, I32, VP, I64, VP, VP, VP, I32, VP, VP, C.c_float, C.c_float,
                                            VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "skyjo_vec_ppo_loss_scratch_bytes": (I64, [I64]),
+    "skyjo_vec_ppo_loss": (C.c_int, [VP, VP, VP, VP, VP, VP, VP, VP, I64, C.c_float, C.c_float, C.c_float, C.c_float, VP, VP, VP,
+                                     VP, I64, VP]),
     "skyjo_vec_rewards_ptr": (VP, [VP]),
     "skyjo_vec_scores_ptr": (VP, [VP]),
     "skyjo_vec_done_ptr": (VP, [VP]),

@@ -16,6 +16,7 @@
 #include "skyjo_policy.h"
 #include "skyjo_targets.h"
 #include "skyjo_batches.h"
+#include "skyjo_loss.h"
 
 // Measurement switches (environment variables: tools/dev/README.md) exist in -DSK_DIAG builds only; the shipped library reads no
 // environment variable at all - what a caller or a test may choose is an option of skyjo_vec_set_option.
@@ -1387,6 +1388,47 @@ int skyjo_vec_rollout_gather(skyjo_vec *h, const void *records, int32_t layout, 
   a.B = h->P.B, a.vstride = value_stride, a.rec_bytes = L.rec_bytes, a.D = L.D, a.Dp = L.Dp;
   a.mean = adv_mean, a.std = adv_std;
   hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((m + SK_GATHER_ROWS - 1) / SK_GATHER_ROWS)), dim3(SK_GATHER_THREADS), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+// ---- the PPO loss head of a learner minibatch (include/skyjo_vec.h: skyjo_vec_ppo_loss; the kernels: skyjo_loss.h) ----
+static constexpr int64_t kLossMaxRows = (int64_t)SK_LOSS_ROWS * 0x7fffffff;
+int64_t skyjo_vec_ppo_loss_scratch_bytes(int64_t m) {
+  if (m < 1 || m > kLossMaxRows) return 0;
+  return (m + SK_LOSS_ROWS - 1) / SK_LOSS_ROWS * (int64_t)(SK_LOSS_STATS * sizeof(double));
+}
+
+int skyjo_vec_ppo_loss(const float *logits, const float *log_mask, const float *value, const int64_t *actions, const float *logp_old,
+                       const float *advantages, const float *value_targets, const float *values_old, int64_t m, float clip,
+                       float vf_coef, float ent_coef, float vf_clip, float *grad_logits_out, float *grad_value_out, double *stats_out,
+                       void *scratch, int64_t scratch_bytes, void *stream) {
+  if (!logits || !log_mask || !value || !actions || !logp_old || !advantages || !value_targets || !values_old || !grad_logits_out ||
+      !grad_value_out || !stats_out || !scratch)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: null argument");
+  if (m < 1 || m > kLossMaxRows) return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: m must be at least 1");
+  if (!std::isfinite(clip) || !(clip > 0.f)) return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: clip must be finite and greater than 0");
+  if (!std::isfinite(vf_coef) || !std::isfinite(ent_coef)) return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: vf_coef and ent_coef must be finite");
+  if ((((uintptr_t)logits | (uintptr_t)log_mask | (uintptr_t)grad_logits_out) & 15) != 0)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: logits, log_mask and grad_logits_out must be 16-byte aligned");
+  if ((((uintptr_t)value | (uintptr_t)logp_old | (uintptr_t)advantages | (uintptr_t)value_targets | (uintptr_t)values_old |
+        (uintptr_t)grad_value_out) & 3) != 0 || (((uintptr_t)actions | (uintptr_t)stats_out | (uintptr_t)scratch) & 7) != 0)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: a column, stats_out or scratch is not aligned to its element size");
+  if (scratch_bytes < skyjo_vec_ppo_loss_scratch_bytes(m)) return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: scratch is smaller than skyjo_vec_ppo_loss_scratch_bytes(m)");
+  static_assert(SK_LOSS_ROWS % 2 == 0 && SK_LOSS_ROWS <= SK_LOSS_THREADS, "a run is whole 16-byte pieces and every row has its lane");
+  SkLossArgs a{};
+  a.logits = logits, a.log_mask = log_mask, a.value = value, a.actions = (const long long *)actions, a.logp_old = logp_old;
+  a.adv = advantages, a.vt = value_targets, a.v_old = values_old, a.g_logits = grad_logits_out, a.g_value = grad_value_out;
+  a.partial = (double *)scratch, a.m = m;
+  a.lo = (float)(1.0 - (double)clip), a.hi = (float)(1.0 + (double)clip);
+  a.vf_coef = vf_coef, a.ent_coef = ent_coef;
+  a.vf_clip = (std::isfinite(vf_clip) && vf_clip > 0.f) ? vf_clip : 0.f;
+  a.inv_m = 1.0f / (float)m;
+  const int64_t nb = (m + SK_LOSS_ROWS - 1) / SK_LOSS_ROWS;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_ppo_loss, dim3((unsigned)nb), dim3(SK_LOSS_THREADS), 0, s, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_ppo_loss_finish, dim3(1), dim3(SK_LOSS_FIN_THREADS), 0, s, (const double *)scratch, (int)nb, (double)m, stats_out);
   HIPCHK(hipGetLastError());
   return SKYJO_OK;
 }

@@ -11,6 +11,7 @@ batches - ``advantages`` and ``value_targets`` by GAE per agent trajectory - in 
 (``skyjo_vec_rollout_targets``).  ``select_rows`` / ``gather_rows`` / ``minibatches`` hand the buffer to a learner: the rows that
 carry a target, the moments of their advantages, and shuffled minibatches as dense float tensors - again on the buffer as it lies
 (``skyjo_vec_rollout_select`` / ``_gather``): no row-major copy of a tile-planar buffer, no knowledge of the record layout.
+``learner.ppo_loss`` takes a ``Minibatch`` and the model's two outputs from there: the PPO loss head and its gradients in one kernel.
 """
 import ctypes as C
 import math
