@@ -378,6 +378,49 @@ int skyjo_vec_sample_actions_layout(skyjo_vec *h, const void *records, int32_t l
 int skyjo_vec_episode_ends_layout(skyjo_vec *h, const void *records, int32_t layout, double *final_rewards_out, uint8_t *episode_end_out,
                                   void *stream);
 
+/* The learner's way back to the matrix cores, in place: an existing net's packed weights rewritten from DEVICE memory by one kernel
+ * launch on `stream` - no allocation, no host copy, no synchronisation; the handle keeps its identity.
+ *
+ * The packed layout (what skyjo_vec_mlp_create builds; fragment = 8 bf16 values = 16 bytes, value j of lane l, hh = l >> 5; S = 2 / ln 2
+ * rounded to float32, bf16(x) = round to nearest even on the bit pattern, every product and difference one rounded float32 operation):
+ *   w1  [8 u][2 s][64 l] fragments   bf16(S * W1[32 u + (l & 31)][k]), k = 16 s + 8 hh + j; k in [obs_dim, 31) holds 0, k = 31 holds b1
+ *   w2  [8 u][16 ks][64 l]           hi(S * W2[32 u + (l & 31)][acc_k]), acc_k = 32 (ks >> 1) + 16 (ks & 1) + 8 (j >> 2) + 4 hh + (j & 3)
+ *   w3  [16 ks][64 l]                hi(W3[l & 31][acc_k]); the rows >= out_dim hold hi(0)
+ *   b2  float32 [256]                S * b2[u];  bf16 mode: + sum over k = 0 .. 255, ascending, in double, of bf16(S * W2[u][k])
+ *   b3  float32 [64 l][16 r]         b3[row], row = (r & 3) + 8 (r >> 2) + 4 hh; bf16 mode: + the same sum of bf16(W3[row][k]); rows >= out_dim 0
+ *   w1l, w2l, w3l                    SKYJO_MLP_FP32 only, the layouts of w1, w2, w3: lo(v) = bf16(v - float(bf16(v))) of the same v
+ * with hi(v) = bf16(v) for SKYJO_MLP_FP32 and bf16(-2 v) for SKYJO_MLP_BF16.
+ *
+ * skyjo_vec_mlp_update: the six arrays are device float32 arrays in torch.nn.Linear layout - [256][obs_dim], [256], [256][256], [256],
+ * [out_dim][256], [out_dim] - with obs_dim, out_dim and the precision the handle was created with; w2 and w3 16-byte aligned.
+ * Afterwards the packed weights hold the bytes skyjo_vec_mlp_create would have produced from the same values, for every finite input.
+ *
+ * skyjo_vec_mlp_adam_step: the same kernel with torch.optim.Adam's rule (no amsgrad, no weight decay) in front of the pack.  Per
+ * element, in float32:  m <- beta1 m + (1 - beta1) g;  v <- beta2 v + (1 - beta2) g^2;
+ *                       p <- p - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps),  t = step (counts from 1).
+ * params[i] / grads[i]: w1, b1, w2, b2, w3, b3 as above (params are rewritten, grads are read only; w2, w3 and their gradients 16-byte
+ * aligned).  The bias corrections are computed on the host, in double, from `step` and the float32 values of beta1 / beta2 as they
+ * are passed; nothing is counted on the device and nothing is read back.  state: caller-owned, 16-byte aligned, at least
+ * skyjo_vec_mlp_adam_state_bytes(m) bytes, zero-filled by the caller before step 1: float32 exp_avg of the six tensors back to
+ * back in that order, padded with zeros to a multiple of 64 floats, then exp_avg_sq the same way.  An element with g == 0 and zero
+ * state keeps its bits.  In bf16 mode the row sums of b2 / b3 are taken from the updated rows in the same launch.
+ * SKYJO_E_INVALID (nothing is launched, the net is unchanged): a null pointer, a misaligned array, state_bytes too small, step < 1,
+ * lr not finite, beta1 or beta2 outside [0, 1), eps negative or not finite.
+ *
+ * Ordering is the stream's: a net launch or rollout queued on the same stream afterwards sees the new weights.  A launch on ANOTHER
+ * stream that still reads the net is the caller's race.
+ *
+ * skyjo_vec_mlp_export (for tests): the pieces copied back to back to dst_device (device, at least skyjo_vec_mlp_packed_bytes(m)
+ * bytes), on `stream`, in the order w1, w2, w3, b2, b3, w1l, w2l, w3l (the *l pieces absent in bf16 mode) - without the padding that
+ * separates them inside the handle, which is uninitialised. */
+int skyjo_vec_mlp_update(skyjo_vec_mlp *m, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+                         const float *b3, void *stream);
+int64_t skyjo_vec_mlp_adam_state_bytes(const skyjo_vec_mlp *m); /* 0 for NULL */
+int skyjo_vec_mlp_adam_step(skyjo_vec_mlp *m, float *const params[6], const float *const grads[6], void *state, int64_t state_bytes,
+                            float lr, float beta1, float beta2, float eps, int64_t step, void *stream);
+int64_t skyjo_vec_mlp_packed_bytes(const skyjo_vec_mlp *m); /* 0 for NULL */
+int skyjo_vec_mlp_export(const skyjo_vec_mlp *m, void *dst_device, int64_t bytes, void *stream);
+
 /* skyjo_vec_step that also does what skyjo_vec_episode_ends does, inside the step kernel (no extra launch): the lane that
  * ends an episode writes episode_end_out[game] = 1 and the game's final rewards, every other game 0 / zeros. */
 int skyjo_vec_step_collect(skyjo_vec *h, const int32_t *actions, void *records_out, double *final_rewards_out,

@@ -104,7 +104,12 @@ SIGNATURES = {
     "skyjo_vec_sample_actions_layout": (C.c_int, [VP, VP, I32, VP, I64, U64, U64, I32, VP, VP, VP, VP]),
     "skyjo_vec_mlp_forward_layout": (C.c_int, [VP, VP, I32, I32, I64, VP, VP]),
     "skyjo_vec_mlp_act_value_layout": (C.c_int, [VP, VP, VP, VP, I32, I64, U64, U64, I32, VP, VP, VP, VP, VP]),
-    "skyjo_vec_step_collect": (C.c_int, [VP, VP, VP, VP, VP, VP]),
+    "skyjo_vec_mlp_update": (C.c_int, [VP, VP, VP, VP, VP, VP, VP, VP]),
+    "skyjo_vec_mlp_adam_state_bytes": (I64, [VP]),
+    "skyjo_vec_mlp_adam_step": (C.c_int, [VP, VP, VP, VP, I64, C.c_float, C.c_float, C.c_float, C.c_float, I64, VP]),
+    "skyjo_vec_mlp_packed_bytes": (I64, [VP]),
+    "skyjo_vec_mlp_export": (C.c_int, [VP, VP, I64, VP]),
+    "skyjo_vec_step_collect":(C.c_int, [VP, VP, VP, VP, VP, VP]),
     "skyjo_vec_model_rollout": (C.c_int, [VP, VP, VP, I32, U64, U64, I32, C.POINTER(RolloutBuffers), VP]),
     "skyjo_vec_rollout_targets": (C.c_int, [VP, VP, I32, I32, VP, I32, VP, VP, C.c_float, C.c_float, VP, VP, VP, VP, VP]),
     "skyjo_vec_rollout_select": (C.c_int, [VP, VP, I64, I32, VP, VP, VP, VP, VP]),

@@ -65,6 +65,13 @@ def sample_actions_fused(model, env, records, seed=0, ticket=0, logp=None):
     return env.sample_actions(logits, records, seed=seed, ticket=ticket, no_masking=model.no_masking, logp=logp)
 
 
+def _device_tensor(name, t, shape, device, dtype=torch.float32):
+    """(``learner._column``'s check, for the tensors the in-place kernels take)"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape {list(shape)} on {device}")
+    return t
+
+
 class FusedNet:
     """One branch of the model (``model.policy`` or ``model.value``: Linear-Tanh-Linear-Tanh-Linear with 256 hidden
     units) packed for the MI355X matrix cores (``skyjo_vec_mlp_*``, csrc/skyjo_policy.hip): weights as bf16 MFMA
@@ -93,6 +100,7 @@ class FusedNet:
                                                 {"bf16": _lib.MLP_BF16, "fp32": _lib.MLP_FP32}[precision],
                                                 *[a.ctypes.data_as(C.c_void_p) for a in arrs], C.byref(h)))
         self._h, self._C, self._check = h, C, _lib.check
+        self.device = int(device)
 
     def __call__(self, records, out=None, planar=False):
         """Outputs float32 [n, out_dim] for the records' games.  ``planar``: ``records`` is tile-planar ([..., tiles, P, 64, 16], what
@@ -131,6 +139,46 @@ class FusedNet:
                                                            1 if no_masking else 0, vp(actions), vp(logp), vp(logits),
                                                            vp(values) if value_net is not None else None, stream))
         return actions
+
+    def branch_parameters(self, seq):
+        """The six parameter tensors of ``seq``'s three ``nn.Linear`` (w1, b1, w2, b2, w3, b3) as ``update`` and ``learner.NativeAdam``
+        hand them to the kernel: checked to be contiguous float32 tensors of this net's shapes on this net's GPU, or ``ValueError``."""
+        if not self._h:
+            raise ValueError("this FusedNet is closed")
+        lins = [m for m in seq if isinstance(m, nn.Linear)]
+        if len(lins) != 3:
+            raise ValueError("seq must hold three nn.Linear")
+        dev = torch.device("cuda", self.device)
+        shapes = ((256, self.obs_dim), (256,), (256, 256), (256,), (self.out_dim, 256), (self.out_dim,))
+        names = ("0.weight", "0.bias", "1.weight", "1.bias", "2.weight", "2.bias")
+        params = [t for lin in lins for t in (lin.weight, lin.bias)]
+        for name, t, shape in zip(names, params, shapes):
+            _device_tensor("linear " + name, t, shape, dev)
+        return params
+
+    def update(self, seq):
+        """Re-pack this net IN PLACE from ``seq``'s parameters as they lie on the net's GPU (``skyjo_vec_mlp_update``): one kernel
+        launch on torch's current stream - no allocation, no host copy, no synchronisation - after which the net holds the bytes
+        ``FusedNet(seq)`` would.  A rollout queued on the same stream afterwards sees the new weights; a launch on another stream
+        that still reads the net is the caller's race.  ``ValueError`` for a parameter of another shape, dtype or device, a
+        non-contiguous one, or a closed net."""
+        params = self.branch_parameters(seq)
+        C = self._C
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            self._check(self._L.skyjo_vec_mlp_update(self._h, *[C.c_void_p(t.data_ptr()) for t in params], stream))
+
+    def export(self):
+        """The packed weights as one uint8 tensor on the net's GPU (``skyjo_vec_mlp_export``: w1, w2, w3, b2, b3 and in "fp32"
+        precision w1l, w2l, w3l, back to back) - what the tests compare byte for byte."""
+        if not self._h:
+            raise ValueError("this FusedNet is closed")
+        C = self._C
+        n = int(self._L.skyjo_vec_mlp_packed_bytes(self._h))
+        with torch.cuda.device(self.device):
+            out = torch.empty((n,), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            self._check(self._L.skyjo_vec_mlp_export(self._h, C.c_void_p(out.data_ptr()), n, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return out
 
     def close(self):
         if self._h:

@@ -14,6 +14,7 @@
 
 #include "skyjo_device.h"
 #include "skyjo_policy.h"
+#include "skyjo_update.h"
 #include "skyjo_targets.h"
 #include "skyjo_batches.h"
 #include "skyjo_loss.h"
@@ -128,7 +129,8 @@ constexpr int deal_interval_default(int num_players, DealForm form, int cycle_s)
 struct skyjo_vec_mlp {
   SkMlpDev net{};
   void *blob = nullptr;
-  int device_id = 0, obs_dim = 0;
+  int device_id = 0, obs_dim = 0, out_dim = 0;
+  size_t offs[8] = {};  // where the pieces lie in the blob (skp_piece_bytes: w1, w2, w3, b2, b3, w1l, w2l, w3l), each at a 256-byte boundary
 };
 
 struct skyjo_vec {
@@ -1125,81 +1127,52 @@ int skyjo_vec_mlp_create(int32_t device_id, int32_t obs_dim, int32_t out_dim, in
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) return fail(SKYJO_E_INVALID, "device_id out of range");
   DevGuard guard_(device_id);
-  auto bf16 = [](float f) {  // round to nearest even
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-  };
-  auto bf16_to_float = [](uint16_t b) {
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-  };
-  auto bf16_lo = [&](float f) {  // what the high half leaves over, again rounded to bf16: f = hi + lo to 16 significant bits
-    const uint32_t hi = (uint32_t)bf16(f) << 16;
-    float fh;
-    memcpy(&fh, &hi, 4);
-    return bf16(f - fh);
-  };
   const bool split = precision == SKYJO_MLP_FP32;
-  // The two hidden layers are stored times 2 / ln 2 (weights AND biases, before the rounding to bf16 / the split into two bf16): their
-  // accumulators are then the exponent of tanh(x) = 1 - 2 / (2^(x 2 / ln 2) + 1) as they stand - no multiply per activation (skyjo_policy.hip)
-  auto acc_k = [](int ks, int hh, int j) { return 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * hh + (j & 3); };
+  // the layout and the packing arithmetic are skyjo_update.h's skp_* helpers: k_mlp_update writes the same bytes from device memory
   const int H = SKP_HIDDEN;
-  const size_t e1 = (size_t)8 * 2 * 64 * 8, e2 = (size_t)8 * 16 * 64 * 8, e3 = (size_t)16 * 64 * 8;
+  const size_t e1 = (size_t)SKU_W1_FRAGS * 8, e2 = (size_t)SKU_W2_FRAGS * 8, e3 = (size_t)SKU_W3_FRAGS * 8;
   std::vector<uint16_t> f1(e1), f2(e2), f3(e3), g1(split ? e1 : 0), g2(split ? e2 : 0), g3(split ? e3 : 0);
   std::vector<float> c2((size_t)H), c3((size_t)64 * 16);
   for (int u = 0; u < 8; u++)
     for (int l = 0; l < 64; l++) {
-      const int m = 32 * u + (l & 31), hh = l >> 5;
+      const int m = skp_row(u, l), hh = l >> 5;
       for (int s = 0; s < 2; s++)
         for (int j = 0; j < 8; j++) {
-          const int k = 16 * s + 8 * hh + j;  // natural order: the kernel builds this operand from the record itself
-          const float v = SKP_SCALE * (k < obs_dim ? w1[(size_t)m * obs_dim + k] : (k == SKP_IN - 1 ? b1[m] : 0.f));
-          const size_t at = (((size_t)u * 2 + s) * 64 + l) * 8 + j;
-          f1[at] = bf16(v);
-          if (split) g1[at] = bf16_lo(v);
+          const float v = skp_w1_value(w1, b1, obs_dim, m, skp_w1_k(s, hh, j));
+          const size_t at = skp_w1_frag(u, s, l) * 8 + j;
+          f1[at] = skp_bf16(v);
+          if (split) g1[at] = skp_bf16_lo(v);
         }
       for (int ks = 0; ks < 16; ks++)
         for (int j = 0; j < 8; j++) {
-          const float v = SKP_SCALE * w2[(size_t)m * H + acc_k(ks, hh, j)];
-          const size_t at = (((size_t)u * 16 + ks) * 64 + l) * 8 + j;
-          // bf16 mode: the layer takes r = (1 - tanh) / 2 of the layer before: - 2 W as weights (exact: a power of two), W 1 joins the bias
-          f2[at] = split ? bf16(v) : bf16(-2.0f * v);
-          if (split) g2[at] = bf16_lo(v);
+          const float v = skp_scaled(w2[(size_t)m * H + skp_acc_k(ks, hh, j)]);
+          const size_t at = skp_w2_frag(u, ks, l) * 8 + j;
+          f2[at] = skp_hi(v, split);
+          if (split) g2[at] = skp_bf16_lo(v);
         }
     }
   for (int l = 0; l < 64; l++) {
     const int m = l & 31, hh = l >> 5;
     for (int ks = 0; ks < 16; ks++)
       for (int j = 0; j < 8; j++) {
-        const float v = m < out_dim ? w3[(size_t)m * H + acc_k(ks, hh, j)] : 0.f;
-        const size_t at = ((size_t)ks * 64 + l) * 8 + j;
-        f3[at] = split ? bf16(v) : bf16(-2.0f * v);
-        if (split) g3[at] = bf16_lo(v);
+        const float v = m < out_dim ? w3[(size_t)m * H + skp_acc_k(ks, hh, j)] : 0.f;
+        const size_t at = skp_w3_frag(ks, l) * 8 + j;
+        f3[at] = skp_hi(v, split);
+        if (split) g3[at] = skp_bf16_lo(v);
       }
     for (int r = 0; r < 16; r++) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * hh;
-      double b = row < out_dim ? (double)b3[row] : 0.0;
-      if (!split && row < out_dim)  // (+ W 1 with the weights as they are stored: bf16-rounded)
-        for (int k = 0; k < H; k++) b += (double)bf16_to_float(bf16(w3[(size_t)row * H + k]));
-      c3[(size_t)l * 16 + r] = (float)b;
+      const int row = skp_b3_row(r, hh);
+      c3[(size_t)l * 16 + r] = row < out_dim ? skp_bias_sum(b3[row], w3 + (size_t)row * H, false, split) : 0.f;
     }
   }
-  for (int u = 0; u < H; u++) {  // (bf16: the accumulator's initial value; float32-grade: the addend in front of the exponential - skyjo_policy.hip)
-    double b = (double)(SKP_SCALE * b2[u]);
-    if (!split)
-      for (int k = 0; k < H; k++) b += (double)bf16_to_float(bf16(SKP_SCALE * w2[(size_t)u * H + k]));
-    c2[u] = (float)b;
-  }
+  // (bf16: the accumulator's initial value; float32-grade: the addend in front of the exponential - skyjo_policy.hip)
+  for (int u = 0; u < H; u++) c2[u] = skp_bias_sum(b2[u], w2 + (size_t)u * H, true, split);
   skyjo_vec_mlp *m = new skyjo_vec_mlp();
   m->device_id = device_id, m->obs_dim = obs_dim;
   struct Piece { const void *src; size_t bytes; };
   const Piece pieces[8] = {{f1.data(), e1 * 2}, {f2.data(), e2 * 2}, {f3.data(), e3 * 2}, {c2.data(), c2.size() * 4}, {c3.data(), c3.size() * 4},
                            {g1.data(), g1.size() * 2}, {g2.data(), g2.size() * 2}, {g3.data(), g3.size() * 2}};
-  size_t total = 0, offs[8];
+  size_t total = 0, *offs = m->offs;
   for (int k = 0; k < 8; k++) offs[k] = total, total += (pieces[k].bytes + 255) & ~(size_t)255;
   if (hipMalloc(&m->blob, total) != hipSuccess) {
     delete m;
@@ -1220,6 +1193,7 @@ int skyjo_vec_mlp_create(int32_t device_id, int32_t obs_dim, int32_t out_dim, in
   m->net.w1l = split ? (const uint4 *)(p + offs[5]) : nullptr, m->net.w2l = split ? (const uint4 *)(p + offs[6]) : nullptr;
   m->net.w3l = split ? (const uint4 *)(p + offs[7]) : nullptr;
   m->net.out_dim = out_dim;
+  m->out_dim = out_dim;
   *out = m;
   return SKYJO_OK;
 }
@@ -1229,6 +1203,92 @@ int skyjo_vec_mlp_destroy(skyjo_vec_mlp *m) {
   DevGuard guard_(m->device_id);
   (void)hipFree(m->blob);
   delete m;
+  return SKYJO_OK;
+}
+
+// ---- the packed net rewritten in place from device memory (include/skyjo_vec.h: skyjo_vec_mlp_update / _adam_step; skyjo_update.h) ----
+namespace {
+
+bool mlp_update_args(const skyjo_vec_mlp *m, const float *const p[SKU_TENSORS], SkUpdArgs &a) {
+  for (int i = 0; i < SKU_TENSORS; i++) {
+    if (!p[i]) return false;
+    a.p[i] = const_cast<float *>(p[i]);
+  }
+  uint8_t *b = (uint8_t *)m->blob;
+  a.f1 = (uint4 *)(b + m->offs[0]), a.f2 = (uint4 *)(b + m->offs[1]), a.f3 = (uint4 *)(b + m->offs[2]);
+  a.c2 = (float *)(b + m->offs[3]), a.c3 = (float *)(b + m->offs[4]);
+  a.g1 = (uint4 *)(b + m->offs[5]), a.g2 = (uint4 *)(b + m->offs[6]), a.g3 = (uint4 *)(b + m->offs[7]);
+  a.obs_dim = m->obs_dim, a.out_dim = m->out_dim, a.split = m->net.split;
+  return true;
+}
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+int skyjo_vec_mlp_update(skyjo_vec_mlp *m, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+                         const float *b3, void *stream) {
+  const float *const p[SKU_TENSORS] = {w1, b1, w2, b2, w3, b3};
+  SkUpdArgs a{};
+  if (!m || !mlp_update_args(m, p, a)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_update: null argument");
+  if (!aligned16(w2) || !aligned16(w3)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_update: w2 and w3 must be 16-byte aligned");
+  DevGuard guard_(m->device_id);
+  hipLaunchKernelGGL(k_mlp_update<false>, dim3(SKU_BLOCKS), dim3(SKU_THREADS), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+int64_t skyjo_vec_mlp_adam_state_bytes(const skyjo_vec_mlp *m) {
+  return m ? (int64_t)(2 * sku_state_half(m->obs_dim, m->out_dim) * sizeof(float)) : 0;
+}
+
+int skyjo_vec_mlp_adam_step(skyjo_vec_mlp *m, float *const params[6], const float *const grads[6], void *state, int64_t state_bytes,
+                            float lr, float beta1, float beta2, float eps, int64_t step, void *stream) {
+  SkUpdArgs a{};
+  if (!m || !params || !grads || !state || !mlp_update_args(m, params, a)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: null argument");
+  for (int i = 0; i < SKU_TENSORS; i++) {
+    if (!grads[i]) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: null gradient");
+    a.g[i] = grads[i];
+    a.off[i] = sku_tensor_offset(i, m->obs_dim, m->out_dim);
+  }
+  if (state_bytes < skyjo_vec_mlp_adam_state_bytes(m))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: state_bytes is less than skyjo_vec_mlp_adam_state_bytes");
+  if (step < 1) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: step counts from 1");
+  if (!std::isfinite(lr)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: lr must be finite");
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: beta1 and beta2 must lie in [0, 1)");
+  if (!(std::isfinite(eps) && eps >= 0.f)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: eps must be finite and not negative");
+  if (!aligned16(state) || !aligned16(params[2]) || !aligned16(params[4]) || !aligned16(grads[2]) || !aligned16(grads[4]))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: state, w2, w3 and their gradients must be 16-byte aligned");
+  a.m = (float *)state, a.v = a.m + sku_state_half(m->obs_dim, m->out_dim);
+  // torch.optim.Adam's scalars, in double from the float32 hyper-parameters and the step, rounded to float32 once
+  const double b1 = (double)beta1, b2 = (double)beta2, t = (double)step;
+  a.w1 = (float)(1.0 - b1), a.beta2 = beta2, a.w2 = (float)(1.0 - b2);
+  a.step_size = (float)((double)lr / (1.0 - std::pow(b1, t)));
+  a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, t));
+  a.eps = eps;
+  DevGuard guard_(m->device_id);
+  hipLaunchKernelGGL(k_mlp_update<true>, dim3(SKU_BLOCKS), dim3(SKU_THREADS), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+int64_t skyjo_vec_mlp_packed_bytes(const skyjo_vec_mlp *m) {
+  if (!m) return 0;
+  size_t n = 0;
+  for (int k = 0; k < 8; k++) n += skp_piece_bytes(k, m->net.split != 0);
+  return (int64_t)n;
+}
+
+int skyjo_vec_mlp_export(const skyjo_vec_mlp *m, void *dst_device, int64_t bytes, void *stream) {
+  if (!m || !dst_device) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_export: null argument");
+  if (bytes < skyjo_vec_mlp_packed_bytes(m)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_export: bytes is less than skyjo_vec_mlp_packed_bytes");
+  DevGuard guard_(m->device_id);
+  size_t at = 0;
+  for (int k = 0; k < 8; k++) {
+    const size_t n = skp_piece_bytes(k, m->net.split != 0);
+    if (!n) continue;
+    HIPCHK(hipMemcpyAsync((uint8_t *)dst_device + at, (const uint8_t *)m->blob + m->offs[k], n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    at += n;
+  }
   return SKYJO_OK;
 }
 

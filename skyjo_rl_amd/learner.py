@@ -1,7 +1,9 @@
 """The learner's loss head on the GPU: ``ppo_loss`` takes the two outputs of ``ActionMaskModel``'s branches on a ``rollout.Minibatch``
 and returns the PPO loss, its statistics and the gradients with respect to both outputs - ONE fused kernel plus a single-workgroup
 reduction (``skyjo_vec_ppo_loss``, csrc/skyjo_loss.h) instead of the chain of small torch expressions and their autograd twins that
-otherwise stands between the model and ``optimizer.step()``.  ``PPOLoss`` wraps it as a ``torch.autograd.Function``.
+otherwise stands between the model and ``optimizer.step()``.  ``PPOLoss`` wraps it as a ``torch.autograd.Function``.  ``NativeAdam`` is the
+step itself: Adam fused with the re-pack of the updated weights into the ``FusedNet``s' MFMA fragments, in place (``skyjo_vec_mlp_adam_step``,
+csrc/skyjo_update.h) - the rollout that follows needs no new nets.
 
 The definition (include/skyjo_vec.h has it in full): the masked softmax of ``action_mask_model.py:58-74`` - logits plus
 the log-mask - the clipped surrogate, the squared value error and the entropy of the PPO the reference trains with
@@ -15,6 +17,7 @@ installed where this package is developed: that form is restated from memory of 
 ``action_mask_model.py`` says of ``TorchFC``).  The gradients are the ones torch's autograd gives for the same expression; the
 statistics are means over the rows, accumulated in double in a fixed order - the same input gives the same bits on every call.
 """
+import ctypes as C
 import math
 from collections import namedtuple
 
@@ -107,3 +110,61 @@ class PPOLoss(torch.autograd.Function):
     def backward(ctx, grad_loss, _grad_stats):
         grad_logits, grad_value = ctx.saved_tensors
         return grad_logits * grad_loss, grad_value * grad_loss, None, None, None, None, None
+
+
+class NativeAdam:
+    """``torch.optim.Adam`` (no amsgrad, no weight decay) for ``model``'s two branches, fused with the re-pack of their ``FusedNet``s:
+    ``step()`` is one ``skyjo_vec_mlp_adam_step`` per branch - two kernel launches on torch's current stream, nothing else.  Each
+    element's thread reads p, g, exp_avg, exp_avg_sq, applies the rule, writes the three back and packs the new p into the net's MFMA
+    fragments in place: when ``step()`` returns, ``policy_net`` and ``value_net`` are queued to hold the updated weights - no
+    ``repack``, no new handles, no host copy, no allocation, no synchronisation.  A rollout on the same stream sees them.
+
+    Duck-typed to what ``examples/ppo.py:ppo_update`` calls on its ``optimizer`` (``zero_grad``, ``step``); not a
+    ``torch.optim.Optimizer``.  ``lr`` is a plain attribute and may be set between steps.  ``lr``, ``betas`` and ``eps`` reach the
+    kernel as float32 (the ABI's type): the bias corrections are computed from the float32 values of the betas.  ``state`` maps a
+    parameter to its ``exp_avg`` / ``exp_avg_sq`` views, as ``torch.optim.Adam.state`` does."""
+
+    def __init__(self, model, policy_net, value_net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        self._L = _lib.load()
+        self.lr, self.betas, self.eps = lr, (float(betas[0]), float(betas[1])), float(eps)
+        self.steps = 0
+        self.state = {}
+        self._branches = []
+        for seq, net in ((model.policy, policy_net), (model.value, value_net)):
+            params = net.branch_parameters(seq)
+            dev = params[0].device
+            n = int(self._L.skyjo_vec_mlp_adam_state_bytes(net._h)) // 4
+            buf = torch.zeros((n,), dtype=torch.float32, device=dev)
+            at = 0
+            for p in params:
+                self.state[p] = {"exp_avg": buf[at:at + p.numel()].view(p.shape), "exp_avg_sq": buf[n // 2 + at:n // 2 + at + p.numel()].view(p.shape)}
+                at += p.numel()
+            pp = (C.c_void_p * 6)(*[p.data_ptr() for p in params])
+            self._branches.append((net, params, buf, pp))
+
+    def zero_grad(self, set_to_none=True):
+        for _, params, _, _ in self._branches:
+            for p in params:
+                if p.grad is None:
+                    continue
+                if set_to_none:
+                    p.grad = None
+                else:
+                    p.grad.detach_().zero_()
+
+    @torch.no_grad()
+    def step(self):
+        calls = []
+        for net, params, buf, pp in self._branches:  # every check before the first launch: both branches step, or neither
+            if not net._h:
+                raise ValueError("a FusedNet of this optimizer is closed")
+            for p in params:
+                if p.grad is None:
+                    raise ValueError("a parameter has no gradient (.grad is None): NativeAdam steps every parameter of both branches")
+                _column("a parameter's .grad", p.grad, torch.float32, tuple(p.shape), p.device)
+            calls.append((net, buf, pp, (C.c_void_p * 6)(*[p.grad.data_ptr() for p in params])))
+        for net, buf, pp, gg in calls:
+            with torch.cuda.device(buf.device):
+                _lib.check(self._L.skyjo_vec_mlp_adam_step(net._h, pp, gg, buf.data_ptr(), buf.numel() * 4, float(self.lr), self.betas[0],
+                                                           self.betas[1], self.eps, self.steps + 1, torch.cuda.current_stream().cuda_stream))
+        self.steps += 1
