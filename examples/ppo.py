@@ -162,8 +162,8 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
 
 
 def repack(model, device=0):
-    """The updated weights as MFMA fragments for the next rollout: (policy FusedNet, value FusedNet) - NEW nets, packed on the host
-    (twelve blocking reads, an allocation, and the old nets to ``close()``).  The in-place way: ``FusedNet.update(seq)`` re-packs an
+    """The updated weights as MFMA fragments for the next rollout: (policy FusedNet, value FusedNet) - NEW nets from host copies of the
+    parameters (twelve blocking reads, two allocations and a synchronise each, and the old nets to ``close()``).  The in-place way: ``FusedNet.update(seq)`` re-packs an
     existing net from the parameters on the GPU in one launch, and ``learner.NativeAdam(model, pol, val, lr=...)`` passed to
     ``ppo_update`` as its ``optimizer`` does that inside every ``step()`` - the nets a rollout holds then never change identity."""
     return FusedNet(model.policy, device=device), FusedNet(model.value, device=device)

@@ -381,7 +381,8 @@ int skyjo_vec_episode_ends_layout(skyjo_vec *h, const void *records, int32_t lay
 /* The learner's way back to the matrix cores, in place: an existing net's packed weights rewritten from DEVICE memory by one kernel
  * launch on `stream` - no allocation, no host copy, no synchronisation; the handle keeps its identity.
  *
- * The packed layout (what skyjo_vec_mlp_create builds; fragment = 8 bf16 values = 16 bytes, value j of lane l, hh = l >> 5; S = 2 / ln 2
+ * The packed layout (one kernel writes it, for skyjo_vec_mlp_create - from its host arrays, staged on the device - and for the calls
+ * below; fragment = 8 bf16 values = 16 bytes, value j of lane l, hh = l >> 5; S = 2 / ln 2
  * rounded to float32, bf16(x) = round to nearest even on the bit pattern, every product and difference one rounded float32 operation):
  *   w1  [8 u][2 s][64 l] fragments   bf16(S * W1[32 u + (l & 31)][k]), k = 16 s + 8 hh + j; k in [obs_dim, 31) holds 0, k = 31 holds b1
  *   w2  [8 u][16 ks][64 l]           hi(S * W2[32 u + (l & 31)][acc_k]), acc_k = 32 (ks >> 1) + 16 (ks & 1) + 8 (j >> 2) + 4 hh + (j & 3)
@@ -393,7 +394,7 @@ int skyjo_vec_episode_ends_layout(skyjo_vec *h, const void *records, int32_t lay
  *
  * skyjo_vec_mlp_update: the six arrays are device float32 arrays in torch.nn.Linear layout - [256][obs_dim], [256], [256][256], [256],
  * [out_dim][256], [out_dim] - with obs_dim, out_dim and the precision the handle was created with; w2 and w3 16-byte aligned.
- * Afterwards the packed weights hold the bytes skyjo_vec_mlp_create would have produced from the same values, for every finite input.
+ * Afterwards the packed weights are the layout above of these values, for every finite input: what skyjo_vec_mlp_create gives for them.
  *
  * skyjo_vec_mlp_adam_step: the same kernel with torch.optim.Adam's rule (no amsgrad, no weight decay) in front of the pack.  Per
  * element, in float32:  m <- beta1 m + (1 - beta1) g;  v <- beta2 v + (1 - beta2) g^2;

@@ -59,6 +59,13 @@ struct DevGuard {
 };
 #define GUARD(h) DevGuard guard_((h)->cfg.device_id)
 
+struct DevBuf {  // a scratch allocation that frees itself
+  void *p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+
 constexpr int kMaxRolloutChunk = 128;  // lockstep iterations per k_step launch (the tile stays in LDS for a whole launch)
 constexpr int kMaxCyclesPerLaunch = 16;  // k_cycle: whole dealing cycles per launch (each of deal_every_iters iterations)
 constexpr size_t kCuLds = 160 * 1024;    // a compute unit's LDS: what a k_cycle workgroup may fill
@@ -130,7 +137,7 @@ struct skyjo_vec_mlp {
   SkMlpDev net{};
   void *blob = nullptr;
   int device_id = 0, obs_dim = 0, out_dim = 0;
-  size_t offs[8] = {};  // where the pieces lie in the blob (skp_piece_bytes: w1, w2, w3, b2, b3, w1l, w2l, w3l), each at a 256-byte boundary
+  SkUpdArgs upd{};  // k_mlp_update's view of the blob and the net's dimensions; a call adds its tensors
 };
 
 struct skyjo_vec {
@@ -1128,72 +1135,35 @@ int skyjo_vec_mlp_create(int32_t device_id, int32_t obs_dim, int32_t out_dim, in
   if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) return fail(SKYJO_E_INVALID, "device_id out of range");
   DevGuard guard_(device_id);
   const bool split = precision == SKYJO_MLP_FP32;
-  // the layout and the packing arithmetic are skyjo_update.h's skp_* helpers: k_mlp_update writes the same bytes from device memory
-  const int H = SKP_HIDDEN;
-  const size_t e1 = (size_t)SKU_W1_FRAGS * 8, e2 = (size_t)SKU_W2_FRAGS * 8, e3 = (size_t)SKU_W3_FRAGS * 8;
-  std::vector<uint16_t> f1(e1), f2(e2), f3(e3), g1(split ? e1 : 0), g2(split ? e2 : 0), g3(split ? e3 : 0);
-  std::vector<float> c2((size_t)H), c3((size_t)64 * 16);
-  for (int u = 0; u < 8; u++)
-    for (int l = 0; l < 64; l++) {
-      const int m = skp_row(u, l), hh = l >> 5;
-      for (int s = 0; s < 2; s++)
-        for (int j = 0; j < 8; j++) {
-          const float v = skp_w1_value(w1, b1, obs_dim, m, skp_w1_k(s, hh, j));
-          const size_t at = skp_w1_frag(u, s, l) * 8 + j;
-          f1[at] = skp_bf16(v);
-          if (split) g1[at] = skp_bf16_lo(v);
-        }
-      for (int ks = 0; ks < 16; ks++)
-        for (int j = 0; j < 8; j++) {
-          const float v = skp_scaled(w2[(size_t)m * H + skp_acc_k(ks, hh, j)]);
-          const size_t at = skp_w2_frag(u, ks, l) * 8 + j;
-          f2[at] = skp_hi(v, split);
-          if (split) g2[at] = skp_bf16_lo(v);
-        }
-    }
-  for (int l = 0; l < 64; l++) {
-    const int m = l & 31, hh = l >> 5;
-    for (int ks = 0; ks < 16; ks++)
-      for (int j = 0; j < 8; j++) {
-        const float v = m < out_dim ? w3[(size_t)m * H + skp_acc_k(ks, hh, j)] : 0.f;
-        const size_t at = skp_w3_frag(ks, l) * 8 + j;
-        f3[at] = skp_hi(v, split);
-        if (split) g3[at] = skp_bf16_lo(v);
-      }
-    for (int r = 0; r < 16; r++) {
-      const int row = skp_b3_row(r, hh);
-      c3[(size_t)l * 16 + r] = row < out_dim ? skp_bias_sum(b3[row], w3 + (size_t)row * H, false, split) : 0.f;
-    }
-  }
-  // (bf16: the accumulator's initial value; float32-grade: the addend in front of the exponential - skyjo_policy.hip)
-  for (int u = 0; u < H; u++) c2[u] = skp_bias_sum(b2[u], w2 + (size_t)u * H, true, split);
   skyjo_vec_mlp *m = new skyjo_vec_mlp();
-  m->device_id = device_id, m->obs_dim = obs_dim;
-  struct Piece { const void *src; size_t bytes; };
-  const Piece pieces[8] = {{f1.data(), e1 * 2}, {f2.data(), e2 * 2}, {f3.data(), e3 * 2}, {c2.data(), c2.size() * 4}, {c3.data(), c3.size() * 4},
-                           {g1.data(), g1.size() * 2}, {g2.data(), g2.size() * 2}, {g3.data(), g3.size() * 2}};
-  size_t total = 0, *offs = m->offs;
-  for (int k = 0; k < 8; k++) offs[k] = total, total += (pieces[k].bytes + 255) & ~(size_t)255;
-  if (hipMalloc(&m->blob, total) != hipSuccess) {
+  m->device_id = device_id, m->obs_dim = m->upd.obs_dim = obs_dim, m->out_dim = m->net.out_dim = m->upd.out_dim = out_dim;
+  if (hipMalloc(&m->blob, skp_piece_offset(8, split)) != hipSuccess) {
     delete m;
     return fail(SKYJO_E_DEVICE, "hipMalloc failed for the packed weights");
   }
-  uint8_t *p = (uint8_t *)m->blob;
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 8 && e == hipSuccess; k++)
-    if (pieces[k].bytes) e = hipMemcpy(p + offs[k], pieces[k].src, pieces[k].bytes, hipMemcpyHostToDevice);
+  // k_mlp_update packs (skyjo_update.h).  The host arrays are staged the way the Adam state lies: tensor i at sku_tensor_offset(i).  Every
+  // tensor in front of w2 and of w3 is a multiple of SKP_HIDDEN floats, so the two are 16-byte aligned as sku_elem4 needs them.
+  static_assert(SKP_HIDDEN % 4 == 0, "w2 and w3 are staged at multiples of SKP_HIDDEN floats: sku_elem4 reads them 16 bytes at a time");
+  skp_blob_views(m->blob, split, m->net, m->upd);
+  const float *const src[SKU_TENSORS] = {w1, b1, w2, b2, w3, b3};
+  SkUpdArgs a = m->upd;
+  DevBuf stage;
+  const char *what = "hipMalloc";
+  hipError_t e = hipMalloc(&stage.p, sku_state_half(obs_dim, out_dim) * sizeof(float));
+  for (int i = 0; i < SKU_TENSORS && e == hipSuccess; i++) {
+    a.p[i] = (float *)stage.p + sku_tensor_offset(i, obs_dim, out_dim);
+    what = "hipMemcpy", e = hipMemcpy(a.p[i], src[i], sku_tensor_elems(i, obs_dim, out_dim) * sizeof(float), hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_mlp_update<false>, dim3(SKU_BLOCKS), dim3(SKU_THREADS), 0, nullptr, a);
+    what = "k_mlp_update", e = hipGetLastError();
+  }
+  if (e == hipSuccess) what = "hipStreamSynchronize", e = hipStreamSynchronize(nullptr);  // (the staging area is freed on return)
   if (e != hipSuccess) {
     (void)hipFree(m->blob);
     delete m;
-    return fail(SKYJO_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    return fail(SKYJO_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
   }
-  m->net.w1 = (const uint4 *)(p + offs[0]), m->net.w2 = (const uint4 *)(p + offs[1]), m->net.w3 = (const uint4 *)(p + offs[2]);
-  m->net.b2 = (const float *)(p + offs[3]), m->net.b3 = (const float *)(p + offs[4]);
-  m->net.split = split ? 1 : 0;
-  m->net.w1l = split ? (const uint4 *)(p + offs[5]) : nullptr, m->net.w2l = split ? (const uint4 *)(p + offs[6]) : nullptr;
-  m->net.w3l = split ? (const uint4 *)(p + offs[7]) : nullptr;
-  m->net.out_dim = out_dim;
-  m->out_dim = out_dim;
   *out = m;
   return SKYJO_OK;
 }
@@ -1210,15 +1180,11 @@ int skyjo_vec_mlp_destroy(skyjo_vec_mlp *m) {
 namespace {
 
 bool mlp_update_args(const skyjo_vec_mlp *m, const float *const p[SKU_TENSORS], SkUpdArgs &a) {
+  a = m->upd;
   for (int i = 0; i < SKU_TENSORS; i++) {
     if (!p[i]) return false;
     a.p[i] = const_cast<float *>(p[i]);
   }
-  uint8_t *b = (uint8_t *)m->blob;
-  a.f1 = (uint4 *)(b + m->offs[0]), a.f2 = (uint4 *)(b + m->offs[1]), a.f3 = (uint4 *)(b + m->offs[2]);
-  a.c2 = (float *)(b + m->offs[3]), a.c3 = (float *)(b + m->offs[4]);
-  a.g1 = (uint4 *)(b + m->offs[5]), a.g2 = (uint4 *)(b + m->offs[6]), a.g3 = (uint4 *)(b + m->offs[7]);
-  a.obs_dim = m->obs_dim, a.out_dim = m->out_dim, a.split = m->net.split;
   return true;
 }
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
@@ -1286,7 +1252,7 @@ int skyjo_vec_mlp_export(const skyjo_vec_mlp *m, void *dst_device, int64_t bytes
   for (int k = 0; k < 8; k++) {
     const size_t n = skp_piece_bytes(k, m->net.split != 0);
     if (!n) continue;
-    HIPCHK(hipMemcpyAsync((uint8_t *)dst_device + at, (const uint8_t *)m->blob + m->offs[k], n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync((uint8_t *)dst_device + at, (const uint8_t *)m->blob + skp_piece_offset(k, m->net.split != 0), n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     at += n;
   }
   return SKYJO_OK;
@@ -1948,12 +1914,6 @@ int skyjo_dev_free(void *p) {
 }
 // ---- the reference's scoring helpers for caller-supplied hands (host pointers; computed on the device) ----
 namespace {
-struct DevBuf {  // a scratch allocation that frees itself
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
 int score_device(int32_t device_id, int *ndev_out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SKYJO_E_NOGPU, "no HIP device visible: this library has no CPU fallback");

@@ -3,11 +3,11 @@
 // skyjo_vec_mlp_adam_step (torch.optim.Adam's rule in front of the pack).  include/skyjo_vec.h and DESIGN.md 4 have the definition;
 // tests/mlp_pack_ref.py restates the layout.
 //
-// (a) The skp_* helpers are __host__ __device__: skyjo_vec_mlp_create (host, scalar) and k_mlp_update (device) pack with the same
-//     statements, so the two give the same bytes for every finite input.  The unit is compiled with -ffp-contract=off: v = SKP_SCALE * w
-//     is one rounded float32 multiply, the bf16 rounding works on the bit pattern, lo = bf16(v - float(hi)) is one rounded subtraction
-//     (float32 subnormals are kept on either side), - 2 v is exact, and the bf16-mode bias sums add the rounded weights of a row in
-//     double in ascending k.
+// (a) There is one packer: k_mlp_update.  skyjo_vec_mlp_create stages its host arrays on the device and runs it too, so the skp_* packing
+//     helpers are device code only.  The unit is compiled with -ffp-contract=off, which makes the kernel's arithmetic the reference's
+//     (tests/mlp_pack_ref.py): v = SKP_SCALE * w is one rounded float32 multiply, the bf16 rounding works on the bit pattern,
+//     lo = bf16(v - float(hi)) is one rounded subtraction (float32 subnormals are kept), - 2 v is exact, and the bf16-mode bias sums add
+//     the rounded weights of a row in double in ascending k.
 // (b) k_mlp_update<ADAM>: SKU_BLOCKS workgroups of SKU_THREADS threads, ONE launch.  Workgroup u < 8 owns the hidden rows 32 u .. 32 u + 31
 //     (the m-tile u of both hidden layers): thread t packs the W2 fragment (u, ks = t / 64, lane = t % 64) - its eight k are two
 //     contiguous float4s of the row, acc_k's order - the first 128 threads also pack a W1 fragment (natural k order, k = 31 is b1), and
@@ -30,47 +30,43 @@
 #define SKU_W3_FRAGS (16 * 64)
 #define SKU_TENSORS 6     // w1, b1, w2, b2, w3, b3
 
-// ---- the layout, for skyjo_vec_mlp_create and the kernel alike ----
-__host__ __device__ inline uint16_t skp_bf16(float f) {  // round to nearest even, on the bit pattern
+// ---- the layout, as k_mlp_update writes it ----
+__device__ inline uint16_t skp_bf16(float f) {  // round to nearest even, on the bit pattern
   uint32_t u;
   memcpy(&u, &f, 4);
   u += 0x7fffu + ((u >> 16) & 1u);
   return (uint16_t)(u >> 16);
 }
-__host__ __device__ inline float skp_bf16_to_float(uint16_t b) {
+__device__ inline float skp_bf16_to_float(uint16_t b) {
   const uint32_t u = (uint32_t)b << 16;
   float f;
   memcpy(&f, &u, 4);
   return f;
 }
 // what the high half leaves over, again rounded to bf16: f = hi + lo to 16 significant bits
-__host__ __device__ inline uint16_t skp_bf16_lo(float f) { return skp_bf16(f - skp_bf16_to_float(skp_bf16(f))); }
+__device__ inline uint16_t skp_bf16_lo(float f) { return skp_bf16(f - skp_bf16_to_float(skp_bf16(f))); }
 
 // The two hidden layers are stored times 2 / ln 2 (weights AND biases, before the rounding to bf16 / the split into two bf16): their
 // accumulators are then the exponent of tanh(x) = 1 - 2 / (2^(x 2 / ln 2) + 1) as they stand - no multiply per activation (skyjo_policy.hip)
-__host__ __device__ inline float skp_scaled(float w) { return SKP_SCALE * w; }
+__device__ inline float skp_scaled(float w) { return SKP_SCALE * w; }
 // the high (or only) half of a weight of layer 2 / 3.  bf16 mode: the layer takes r = (1 - tanh) / 2 of the layer before: - 2 W as
 // weights (exact: a power of two), W 1 joins the bias (skp_bias_sum)
-__host__ __device__ inline uint16_t skp_hi(float v, bool split) { return split ? skp_bf16(v) : skp_bf16(-2.0f * v); }
+__device__ inline uint16_t skp_hi(float v, bool split) { return split ? skp_bf16(v) : skp_bf16(-2.0f * v); }
 
 // element j of the fragment of lane l: which k it holds.  Layer 1 in natural order (the kernel builds that operand from the record
 // itself), layers 2 and 3 in the order the accumulators of the layer before come out (hh = l >> 5)
-__host__ __device__ inline int skp_w1_k(int s, int hh, int j) { return 16 * s + 8 * hh + j; }
-__host__ __device__ inline int skp_acc_k(int ks, int hh, int j) { return 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * hh + (j & 3); }
-__host__ __device__ inline int skp_row(int u, int l) { return 32 * u + (l & 31); }
+__device__ inline int skp_w1_k(int s, int hh, int j) { return 16 * s + 8 * hh + j; }
+__device__ inline int skp_acc_k(int ks, int hh, int j) { return 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * hh + (j & 3); }
+__device__ inline int skp_row(int u, int l) { return 32 * u + (l & 31); }
 // where a fragment lies, counted in fragments of 8 values
-__host__ __device__ inline size_t skp_w1_frag(int u, int s, int l) { return ((size_t)u * 2 + s) * 64 + l; }
-__host__ __device__ inline size_t skp_w2_frag(int u, int ks, int l) { return ((size_t)u * 16 + ks) * 64 + l; }
-__host__ __device__ inline size_t skp_w3_frag(int ks, int l) { return (size_t)ks * 64 + l; }
+__device__ inline size_t skp_w1_frag(int u, int s, int l) { return ((size_t)u * 2 + s) * 64 + l; }
+__device__ inline size_t skp_w2_frag(int u, int ks, int l) { return ((size_t)u * 16 + ks) * 64 + l; }
+__device__ inline size_t skp_w3_frag(int ks, int l) { return (size_t)ks * 64 + l; }
 // b3 lies in accumulator layout, [64 lanes][16 registers]: the output row of register r of a lane of half hh
-__host__ __device__ inline int skp_b3_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-// layer 1's value at (row m, k): the weight, the bias at k = 31, zero between
-__host__ __device__ inline float skp_w1_value(const float *w1, const float *b1, int obs_dim, int m, int k) {
-  return skp_scaled(k < obs_dim ? w1[(size_t)m * obs_dim + k] : (k == SKP_IN - 1 ? b1[m] : 0.f));
-}
+__device__ inline int skp_b3_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 // b2's entry (scaled = true) or a row bias of b3: the bias, and in bf16 mode + W 1 with the row's weights as they are stored:
 // bf16-rounded, added in double in ascending k
-__host__ __device__ inline float skp_bias_sum(float bias, const float *row, bool scaled, bool split) {
+__device__ inline float skp_bias_sum(float bias, const float *row, bool scaled, bool split) {
   double b = (double)(scaled ? skp_scaled(bias) : bias);
   if (!split)
     for (int k = 0; k < SKP_HIDDEN; k++) b += (double)skp_bf16_to_float(skp_bf16(scaled ? skp_scaled(row[k]) : row[k]));
@@ -78,7 +74,7 @@ __host__ __device__ inline float skp_bias_sum(float bias, const float *row, bool
 }
 
 // The pieces of the blob, in the order skyjo_vec_mlp_export writes them: w1, w2, w3, b2, b3, w1l, w2l, w3l (bytes; the *l pieces are
-// empty in bf16 mode).
+// empty in bf16 mode).  In a skyjo_vec_mlp's blob each starts at a 256-byte boundary: skp_piece_offset, piece 8 being the blob's size.
 __host__ __device__ inline size_t skp_piece_bytes(int piece, bool split) {
   switch (piece) {
     case 0: return (size_t)SKU_W1_FRAGS * 16;
@@ -90,6 +86,11 @@ __host__ __device__ inline size_t skp_piece_bytes(int piece, bool split) {
     case 6: return split ? (size_t)SKU_W2_FRAGS * 16 : 0;
     default: return split ? (size_t)SKU_W3_FRAGS * 16 : 0;
   }
+}
+__host__ __device__ inline size_t skp_piece_offset(int piece, bool split) {
+  size_t o = 0;
+  for (int k = 0; k < piece; k++) o += (skp_piece_bytes(k, split) + 255) & ~(size_t)255;
+  return o;
 }
 
 // ---- the Adam state of one net: exp_avg of the six tensors back to back, padded to SKU_STATE_ALIGN floats, then exp_avg_sq ----
@@ -125,6 +126,18 @@ struct SkUpdArgs {
   // torch.optim.Adam's scalars, rounded to float32 once on the host: 1 - beta1, beta2, 1 - beta2, lr / (1 - beta1^t), sqrt(1 - beta2^t), eps
   float w1, beta2, w2, step_size, bc2_sqrt, eps;
 };
+
+// both views of a blob, from its base: the net kernels' (read only; no low halves in bf16 mode) and k_mlp_update's
+inline void skp_blob_views(void *blob, bool split, SkMlpDev &net, SkUpdArgs &a) {
+  uint8_t *b = (uint8_t *)blob;
+  net.w1 = a.f1 = (uint4 *)(b + skp_piece_offset(0, split)), net.w2 = a.f2 = (uint4 *)(b + skp_piece_offset(1, split));
+  net.w3 = a.f3 = (uint4 *)(b + skp_piece_offset(2, split));
+  net.b2 = a.c2 = (float *)(b + skp_piece_offset(3, split)), net.b3 = a.c3 = (float *)(b + skp_piece_offset(4, split));
+  net.w1l = a.g1 = split ? (uint4 *)(b + skp_piece_offset(5, split)) : nullptr;
+  net.w2l = a.g2 = split ? (uint4 *)(b + skp_piece_offset(6, split)) : nullptr;
+  net.w3l = a.g3 = split ? (uint4 *)(b + skp_piece_offset(7, split)) : nullptr;
+  net.split = a.split = split ? 1 : 0;
+}
 
 // torch.optim.Adam (no amsgrad, no weight decay) on one element, in torch's single-tensor operation order:
 //   m <- m + (g - m) (1 - beta1);  v <- v beta2 + ((1 - beta2) g) g;  p <- p + (-step_size m) / (sqrt(v) / sqrt(1 - beta2^t) + eps)

@@ -62,6 +62,19 @@ def test_repack_equals_create_equals_ref(precision, obs_dim, out_dim):
     net.close()
 
 
+def test_two_creates_back_to_back_keep_their_own_bytes():
+    """Nothing of one create (its staging area, its launch) outlives the call: the first net is read after the second exists."""
+    import torch
+    from skyjo_rl_amd.action_mask_model import FusedNet
+
+    cases = (("fp32", 31, 26, 0), ("bf16", 1, 32, 1))
+    weights = [_default_init(o, d, seed) for _, o, d, seed in cases]
+    nets = [FusedNet(_seq(w, o, d), precision=p) for w, (p, o, d, _) in zip(weights, cases)]
+    for net, w, (p, _, _, _) in zip(nets, weights, cases):
+        assert _same(net.export(), torch.from_numpy(ref.pack(*w, precision=p)).cuda()), p
+        net.close()
+
+
 @case
 def test_outputs_after_update_are_a_fresh_nets(precision, obs_dim, out_dim):
     import torch
@@ -103,7 +116,7 @@ def _adam_run(precision, obs_dim, out_dim):
     opt = NativeAdam(model, nets[0], nets[1], **ref.ADAM_HYPER)
     branches = [list(model.policy.parameters()), list(model.value.parameters())]
     zero_p = branches[0][ref.ADAM_ZERO_TENSOR].detach().clone()
-    frag = []
+    frag, packed = [], []
     for t in range(1, ref.ADAM_STEPS + 1):
         for b, params in enumerate(branches):
             for p, g in zip(params, ref.adam_grads([tuple(p.shape) for p in params], t, seed=77 + b)):
@@ -113,8 +126,10 @@ def _adam_run(precision, obs_dim, out_dim):
             fresh = FusedNet(seq, precision=precision)  # (created from the parameters as they now are, read back)
             frag.append((t, b, _same(nets[b].export(), fresh.export())))
             fresh.close()
+            want = ref.pack(*[p.detach().cpu().numpy() for p in branches[b]], precision=precision)  # (the layout's own statement)
+            packed.append((t, b, _same(nets[b].export(), torch.from_numpy(want).cuda())))
     pol = branches[0]
-    _RUNS[key] = {"frag": frag, "steps": opt.steps,
+    _RUNS[key] = {"frag": frag, "packed": packed, "steps": opt.steps,
                   "p": [p.detach().cpu().numpy() for p in pol],
                   "exp_avg": [opt.state[p]["exp_avg"].cpu().numpy() for p in pol],
                   "exp_avg_sq": [opt.state[p]["exp_avg_sq"].cpu().numpy() for p in pol],
@@ -129,6 +144,7 @@ def test_adam_fragments_are_a_fresh_nets_after_every_step(precision, obs_dim, ou
     run = _adam_run(precision, obs_dim, out_dim)
     assert run["steps"] == ref.ADAM_STEPS and len(run["frag"]) == 2 * ref.ADAM_STEPS
     assert all(ok for _, _, ok in run["frag"]), run["frag"]
+    assert len(run["packed"]) == 2 * ref.ADAM_STEPS and all(ok for _, _, ok in run["packed"]), run["packed"]
 
 
 @case

@@ -1,6 +1,6 @@
 """The learner step's way back to the matrix cores, in place against the path it replaces, on the example's model (31-256-256-26 policy and
 31-256-256-1 value branch, float32-grade nets).  Per learner step, with gradients already in ``.grad``:
-  parent  ``torch.optim.Adam.step()``, then ``close()`` of both nets and ``examples.ppo.repack(model)``: new nets packed on the host
+  parent  ``torch.optim.Adam.step()``, then ``close()`` of both nets and ``examples.ppo.repack(model)``: new nets through the host
   native  ``learner.NativeAdam.step()``: Adam and the re-pack of both branches in two launches (skyjo_vec_mlp_adam_step)
 and the re-pack alone:
   create  ``FusedNet(seq)`` + ``close()``            update  ``FusedNet.update(seq)``
