@@ -7,15 +7,20 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(ROOT, "include", "skyjo_vec.h")]
-# Two translation units, each with the instruction scheduler that suits it (EXPERIMENTS.md round 5 #11, round 6): the
-# environment kernels gain 1 - 2 % under max-ilp, the policy net's hand-placed MFMA gaps want the default strategy.
-UNITS = [("skyjo_capi", os.path.join(CSRC, "skyjo_capi.hip"), ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
+# Three translation units.  The environment's and the policy net's each have the instruction scheduler that suits them (EXPERIMENTS.md
+# round 5 #11, round 6): the environment kernels gain 1 - 2 % under max-ilp, the policy net's hand-placed MFMA gaps want the default
+# strategy.  The learner's (the packed nets' handles, targets, minibatches, loss, update) keeps the flags its kernels were built with
+# while they lived in the environment's unit; it is a unit of its own so that learner work changes neither the environment's sources
+# nor its code object.
+MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+UNITS = [("skyjo_capi", os.path.join(CSRC, "skyjo_capi.hip"), MAX_ILP),
+         ("skyjo_learner", os.path.join(CSRC, "skyjo_learner.hip"), MAX_ILP),
          # (the net kernels are straight-line code: their gap loops must unroll completely, whatever the size)
          ("skyjo_policy", os.path.join(CSRC, "skyjo_policy.hip"), ["-mllvm", "-unroll-threshold=100000", "-mllvm", "-pragma-unroll-threshold=1000000"])]
 SRC = UNITS[0][1]
 DEPS = [u[1] for u in UNITS] + HEADERS
 OUT = os.path.join(HERE, "libskyjo_vec.so")
-OBJ_DIR = os.path.join(HERE, "_obj")  # (object files of the two units; git-ignored, not sent to the GPU box)
+OBJ_DIR = os.path.join(HERE, "_obj")  # (object files of the units; git-ignored)
 
 # -ffp-contract=off: rewards are float64 and must round exactly like numpy (no fused multiply-add); the policy unit shares the
 # masked draw's float32 arithmetic with the environment unit (skyjo_draw.h) and must round like it
@@ -29,7 +34,7 @@ def needs_build():
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in DEPS)
 
 
-def build(force=False, verbose=False, extra=(), out=None, jobs=2):
+def build(force=False, verbose=False, extra=(), out=None, jobs=min(len(UNITS), 16)):
     """Compile the units (in parallel) and link them into `out` (default: libskyjo_vec.so next to this file)."""
     out = out or OUT
     if not force and out == OUT and not needs_build():

@@ -1,5 +1,5 @@
-// skyjo_batches.h - part of skyjo_device.h's family (included from skyjo_capi.hip after skyjo_targets.h: it reads records through
-// sk_rec_byte of skyjo_callers.h).  Learner minibatches of a rollout buffer: which rows take part (with the moments of their
+// skyjo_batches.h - learner kernels (included from skyjo_learner.hip; they read records through sk_rec_byte of skyjo_layout.h and are no
+// part of the environment's sources).  Learner minibatches of a rollout buffer: which rows take part (with the moments of their
 // advantages), and the rows of a minibatch as the dense float tensors a learner feeds its model - both on the buffer as it lies,
 // in either record layout.
 //
@@ -16,10 +16,12 @@
 //     offset is no multiple of 16).  The columns are one lane per row.  A row id outside [0, T * B) reads nothing and gives an
 //     all-zero output row.  No private segment.
 #pragma once
-#ifndef SKYJO_DEVICE_PARTS
-#error "include skyjo_device.h first"
-#endif
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
 #include <cfloat>
+
+#include "skyjo_layout.h"
 
 #define SK_SEL_THREADS 256
 #define SK_SEL_WAVES (SK_SEL_THREADS / 64)

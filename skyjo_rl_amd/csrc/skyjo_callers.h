@@ -11,11 +11,6 @@
 // stretch that is copied to LDS with coalesced 16-byte loads; a lane then walks its own row (stride 26 words:
 // two lanes per bank).  The mask bytes come straight out of the engine's records.
 // ------------------------------------------------------------------------------------------
-// Byte k of record r in either layout.  `planar`: the records lie tile-planar
-// (SKYJO_REC_TILE_PLANAR: byte k of record r at  (r / 64) * 64 * rec_bytes + (k / 16) * 1024 + (r % 64) * 16 + k % 16).
-__device__ __forceinline__ const uint8_t *sk_rec_byte(const uint8_t *rec, long long r, int k, int rec_bytes, int planar) {
-  return planar ? rec + (r >> 6) * (64LL * rec_bytes) + (long long)(k >> 4) * 1024 + (r & 63) * 16 + (k & 15) : rec + r * rec_bytes + k;
-}
 #define SK_SAMPLE_BLOCK 256
 __global__ __launch_bounds__(SK_SAMPLE_BLOCK) void k_sample(SkLayout L, const uint8_t *rec, const float *logits, long long n,
                                                             uint64_t seed, uint64_t ticket, uint64_t game_id0, int no_masking,

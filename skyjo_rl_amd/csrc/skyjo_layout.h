@@ -77,3 +77,12 @@ SK_HD static inline SkLayout sk_make_layout(int N, int indirect) {
   return L;
 }
 SK_HD static inline int sk_pb(const SkLayout &L, int p) { return L.off_players + PB_BYTES * p; }
+
+#ifdef __HIPCC__
+// ---- records as the kernels write them, outside a game's packed state (the environment's and the learner's kernels read them) ----
+// Byte k of record r in either layout.  `planar`: the records lie tile-planar
+// (SKYJO_REC_TILE_PLANAR: byte k of record r at  (r / 64) * 64 * rec_bytes + (k / 16) * 1024 + (r % 64) * 16 + k % 16).
+__device__ __forceinline__ const uint8_t *sk_rec_byte(const uint8_t *rec, long long r, int k, int rec_bytes, int planar) {
+  return planar ? rec + (r >> 6) * (64LL * rec_bytes) + (long long)(k >> 4) * 1024 + (r & 63) * 16 + (k & 15) : rec + r * rec_bytes + k;
+}
+#endif

@@ -1,0 +1,344 @@
+// skyjo_learner.hip - the packed nets' handles and the learner behind the extern "C" boundary of include/skyjo_vec.h: skyjo_vec_mlp_*,
+// skyjo_vec_rollout_targets / _select / _gather and skyjo_vec_ppo_loss, with their kernels (skyjo_update.h, skyjo_targets.h,
+// skyjo_batches.h, skyjo_loss.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
+// (skyjo_capi.hip, skyjo_device.h and its parts), and of an engine it sees what skyjo_host.h shows - the record layout, B, G, game_id0,
+// the device and the select scratch.  gfx950 only, no CPU path.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <new>
+#include <string>
+
+#include "skyjo_host.h"
+#include "skyjo_update.h"
+#include "skyjo_targets.h"
+#include "skyjo_batches.h"
+#include "skyjo_loss.h"
+
+extern "C" {
+
+int skyjo_vec_mlp_create(int32_t device_id, int32_t obs_dim, int32_t out_dim, int32_t precision, const float *w1, const float *b1,
+                         const float *w2, const float *b2, const float *w3, const float *b3, skyjo_vec_mlp **out) {
+  if (!out || !w1 || !b1 || !w2 || !b2 || !w3 || !b3) return fail(SKYJO_E_INVALID, "null argument");
+  if (obs_dim < 1 || obs_dim > SKP_IN - 1 || out_dim < 1 || out_dim > SKP_OUT)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_mlp: obs_dim must be 1..31 and out_dim 1..32");
+  if (precision != SKYJO_MLP_BF16 && precision != SKYJO_MLP_FP32) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp: unknown precision");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) return fail(SKYJO_E_INVALID, "device_id out of range");
+  DevGuard guard_(device_id);
+  const bool split = precision == SKYJO_MLP_FP32;
+  skyjo_vec_mlp *m = new skyjo_vec_mlp();
+  m->device_id = device_id, m->obs_dim = obs_dim, m->out_dim = m->net.out_dim = out_dim;
+  if (hipMalloc(&m->blob, skp_piece_offset(8, split)) != hipSuccess) {
+    delete m;
+    return fail(SKYJO_E_DEVICE, "hipMalloc failed for the packed weights");
+  }
+  // k_mlp_update packs (skyjo_update.h).  The host arrays are staged the way the Adam state lies: tensor i at sku_tensor_offset(i).  Every
+  // tensor in front of w2 and of w3 is a multiple of SKP_HIDDEN floats, so the two are 16-byte aligned as sku_elem4 needs them.
+  static_assert(SKP_HIDDEN % 4 == 0, "w2 and w3 are staged at multiples of SKP_HIDDEN floats: sku_elem4 reads them 16 bytes at a time");
+  SkUpdArgs a{};
+  skp_blob_views(m->blob, split, m->net, a);
+  a.obs_dim = obs_dim, a.out_dim = out_dim;
+  const float *const src[SKU_TENSORS] = {w1, b1, w2, b2, w3, b3};
+  DevBuf stage;
+  const char *what = "hipMalloc";
+  hipError_t e = hipMalloc(&stage.p, sku_state_half(obs_dim, out_dim) * sizeof(float));
+  for (int i = 0; i < SKU_TENSORS && e == hipSuccess; i++) {
+    a.p[i] = (float *)stage.p + sku_tensor_offset(i, obs_dim, out_dim);
+    what = "hipMemcpy", e = hipMemcpy(a.p[i], src[i], sku_tensor_elems(i, obs_dim, out_dim) * sizeof(float), hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_mlp_update<false>, dim3(SKU_BLOCKS), dim3(SKU_THREADS), 0, nullptr, a);
+    what = "k_mlp_update", e = hipGetLastError();
+  }
+  if (e == hipSuccess) what = "hipStreamSynchronize", e = hipStreamSynchronize(nullptr);  // (the staging area is freed on return)
+  if (e != hipSuccess) {
+    (void)hipFree(m->blob);
+    delete m;
+    return fail(SKYJO_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+  }
+  *out = m;
+  return SKYJO_OK;
+}
+
+int skyjo_vec_mlp_destroy(skyjo_vec_mlp *m) {
+  if (!m) return SKYJO_OK;
+  DevGuard guard_(m->device_id);
+  (void)hipFree(m->blob);
+  delete m;
+  return SKYJO_OK;
+}
+
+// ---- the packed net rewritten in place from device memory (include/skyjo_vec.h: skyjo_vec_mlp_update / _adam_step; skyjo_update.h) ----
+namespace {
+
+// k_mlp_update's view of the blob and the net's dimensions, with a call's tensors
+bool mlp_update_args(const skyjo_vec_mlp *m, const float *const p[SKU_TENSORS], SkUpdArgs &a) {
+  SkMlpDev net{};  // (the net kernels' view of the same blob: m->net holds it already)
+  skp_blob_views(m->blob, m->net.split != 0, net, a);
+  a.obs_dim = m->obs_dim, a.out_dim = m->out_dim;
+  for (int i = 0; i < SKU_TENSORS; i++) {
+    if (!p[i]) return false;
+    a.p[i] = const_cast<float *>(p[i]);
+  }
+  return true;
+}
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+int skyjo_vec_mlp_update(skyjo_vec_mlp *m, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+                         const float *b3, void *stream) {
+  const float *const p[SKU_TENSORS] = {w1, b1, w2, b2, w3, b3};
+  SkUpdArgs a{};
+  if (!m || !mlp_update_args(m, p, a)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_update: null argument");
+  if (!aligned16(w2) || !aligned16(w3)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_update: w2 and w3 must be 16-byte aligned");
+  DevGuard guard_(m->device_id);
+  hipLaunchKernelGGL(k_mlp_update<false>, dim3(SKU_BLOCKS), dim3(SKU_THREADS), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+int64_t skyjo_vec_mlp_adam_state_bytes(const skyjo_vec_mlp *m) {
+  return m ? (int64_t)(2 * sku_state_half(m->obs_dim, m->out_dim) * sizeof(float)) : 0;
+}
+
+int skyjo_vec_mlp_adam_step(skyjo_vec_mlp *m, float *const params[6], const float *const grads[6], void *state, int64_t state_bytes,
+                            float lr, float beta1, float beta2, float eps, int64_t step, void *stream) {
+  SkUpdArgs a{};
+  if (!m || !params || !grads || !state || !mlp_update_args(m, params, a)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: null argument");
+  for (int i = 0; i < SKU_TENSORS; i++) {
+    if (!grads[i]) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: null gradient");
+    a.g[i] = grads[i];
+    a.off[i] = sku_tensor_offset(i, m->obs_dim, m->out_dim);
+  }
+  if (state_bytes < skyjo_vec_mlp_adam_state_bytes(m))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: state_bytes is less than skyjo_vec_mlp_adam_state_bytes");
+  if (step < 1) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: step counts from 1");
+  if (!std::isfinite(lr)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: lr must be finite");
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: beta1 and beta2 must lie in [0, 1)");
+  if (!(std::isfinite(eps) && eps >= 0.f)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: eps must be finite and not negative");
+  if (!aligned16(state) || !aligned16(params[2]) || !aligned16(params[4]) || !aligned16(grads[2]) || !aligned16(grads[4]))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: state, w2, w3 and their gradients must be 16-byte aligned");
+  a.m = (float *)state, a.v = a.m + sku_state_half(m->obs_dim, m->out_dim);
+  // torch.optim.Adam's scalars, in double from the float32 hyper-parameters and the step, rounded to float32 once
+  const double b1 = (double)beta1, b2 = (double)beta2, t = (double)step;
+  a.w1 = (float)(1.0 - b1), a.beta2 = beta2, a.w2 = (float)(1.0 - b2);
+  a.step_size = (float)((double)lr / (1.0 - std::pow(b1, t)));
+  a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, t));
+  a.eps = eps;
+  DevGuard guard_(m->device_id);
+  hipLaunchKernelGGL(k_mlp_update<true>, dim3(SKU_BLOCKS), dim3(SKU_THREADS), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+int64_t skyjo_vec_mlp_packed_bytes(const skyjo_vec_mlp *m) {
+  if (!m) return 0;
+  size_t n = 0;
+  for (int k = 0; k < 8; k++) n += skp_piece_bytes(k, m->net.split != 0);
+  return (int64_t)n;
+}
+
+int skyjo_vec_mlp_export(const skyjo_vec_mlp *m, void *dst_device, int64_t bytes, void *stream) {
+  if (!m || !dst_device) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_export: null argument");
+  if (bytes < skyjo_vec_mlp_packed_bytes(m)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_export: bytes is less than skyjo_vec_mlp_packed_bytes");
+  DevGuard guard_(m->device_id);
+  size_t at = 0;
+  for (int k = 0; k < 8; k++) {
+    const size_t n = skp_piece_bytes(k, m->net.split != 0);
+    if (!n) continue;
+    HIPCHK(hipMemcpyAsync((uint8_t *)dst_device + at, (const uint8_t *)m->blob + skp_piece_offset(k, m->net.split != 0), n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    at += n;
+  }
+  return SKYJO_OK;
+}
+
+int skyjo_vec_mlp_forward_layout(const skyjo_vec_mlp *m, const void *records, int32_t record_bytes, int32_t layout, int64_t n, float *out,
+                                 void *stream) {
+  if (!m || !records || !out || n < 0 || record_bytes < 32 || (record_bytes & 15))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_forward: bad argument");
+  if (int rc = check_layout(layout)) return rc;
+  if (n == 0) return SKYJO_OK;
+  DevGuard guard_(m->device_id);
+  SkMlpDraw nodraw{};
+  return launch_mlp(m, m, 1, (const uint8_t *)records, (int)record_bytes, m->obs_dim, n, out, nodraw, nullptr, (hipStream_t)stream,
+                    (int)(layout == SKYJO_REC_TILE_PLANAR));
+}
+int skyjo_vec_mlp_forward(const skyjo_vec_mlp *m, const void *records, int32_t record_bytes, int64_t n, float *out,
+                          void *stream) {
+  return skyjo_vec_mlp_forward_layout(m, records, record_bytes, SKYJO_REC_ROW_MAJOR, n, out, stream);
+}
+
+int skyjo_vec_mlp_act_value_layout(skyjo_vec *h, const skyjo_vec_mlp *policy, const skyjo_vec_mlp *value, const void *records, int32_t layout,
+                                   int64_t n, uint64_t seed, uint64_t ticket, int32_t no_masking, int32_t *actions_out, float *logp_out,
+                                   float *logits_out, float *values_out, void *stream) {
+  if (!h || !policy || !records || !actions_out || n < 0 || (value && !values_out))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_act_value: bad argument");
+  if (int rc = check_layout(layout)) return rc;
+  const SkEngineView e = sk_engine_view(h);
+  DevGuard guard_(e.device_id);
+  if (policy->net.out_dim != SKYJO_NUM_ACTIONS) return fail(SKYJO_E_INVALID, "the policy net needs 26 outputs");
+  if (value && (policy->obs_dim != value->obs_dim || policy->device_id != value->device_id || policy->device_id != e.device_id ||
+                policy->net.split != value->net.split))
+    return fail(SKYJO_E_INVALID, "policy and value net must share the observation size, the precision and the engine's device");
+  if (n == 0) return SKYJO_OK;
+  SkMlpDraw d{};
+  d.enable = 1, d.mask_offset = e.L->Dp, d.no_masking = no_masking, d.seed = seed, d.ticket = ticket;
+  d.game_id0 = e.game_id0, d.actions = actions_out, d.logp = logp_out;
+  return launch_mlp(policy, value ? value : policy, value ? 2 : 1, (const uint8_t *)records, (int)e.L->rec_bytes, policy->obs_dim, n, logits_out,
+                    d, value ? values_out : nullptr, (hipStream_t)stream, (int)(layout == SKYJO_REC_TILE_PLANAR));
+}
+int skyjo_vec_mlp_act(skyjo_vec *h, const skyjo_vec_mlp *m, const void *records, int64_t n, uint64_t seed, uint64_t ticket,
+                      int32_t no_masking, int32_t *actions_out, float *logp_out, float *logits_out, void *stream) {
+  if (!m) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_act: bad argument");
+  return skyjo_vec_mlp_act_value_layout(h, m, nullptr, records, SKYJO_REC_ROW_MAJOR, n, seed, ticket, no_masking, actions_out, logp_out, logits_out,
+                                        nullptr, stream);
+}
+int skyjo_vec_mlp_act_value(skyjo_vec *h, const skyjo_vec_mlp *policy, const skyjo_vec_mlp *value, const void *records, int64_t n,
+                            uint64_t seed, uint64_t ticket, int32_t no_masking, int32_t *actions_out, float *logp_out,
+                            float *logits_out, float *values_out, void *stream) {
+  if (!value || !values_out) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_act_value: bad argument");
+  return skyjo_vec_mlp_act_value_layout(h, policy, value, records, SKYJO_REC_ROW_MAJOR, n, seed, ticket, no_masking, actions_out, logp_out,
+                                        logits_out, values_out, stream);
+}
+
+// ---- learner targets of a rollout buffer (include/skyjo_vec.h: skyjo_vec_rollout_targets; the kernel: skyjo_targets.h) ----
+int skyjo_vec_rollout_targets(skyjo_vec *h, const void *records, int32_t layout, int32_t T, const float *values, int32_t value_stride,
+                              const double *final_rewards, const uint8_t *episode_end, float gamma, float lambda, float *advantages_out,
+                              float *value_targets_out, float *returns_out, uint8_t *flags_out, void *stream) {
+  if (!h || !records || !values || !final_rewards || !episode_end || !advantages_out || !value_targets_out || !returns_out || !flags_out)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_targets: null argument");
+  if (T < 1 || value_stride < 1) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_targets: T and value_stride must be at least 1");
+  if (!(gamma >= 0.f && gamma <= 1.f) || !(lambda >= 0.f && lambda <= 1.f))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_targets: gamma and lambda must lie in [0, 1]");
+  if (int rc = check_layout(layout)) return rc;
+  const SkEngineView e = sk_engine_view(h);
+  DevGuard guard_(e.device_id);
+  const SkLayout &L = *e.L;
+  SkTargetsArgs a{};
+  a.rec = (const uint8_t *)records, a.values = values, a.rewards = final_rewards, a.end = episode_end;
+  a.adv = advantages_out, a.vt = value_targets_out, a.ret = returns_out, a.flags = flags_out;
+  a.planar = layout == SKYJO_REC_TILE_PLANAR;
+  a.rec_stride = a.planar ? (long long)e.G : (long long)e.B;
+  a.B = e.B, a.T = T, a.N = L.N, a.vstride = value_stride, a.rec_bytes = L.rec_bytes;
+  a.off_agent = L.Dp + 26, a.off_done = L.Dp + 28;
+  a.gamma = gamma, a.gl = gamma * lambda;  // (float32 product, rounded once: part of the definition)
+  const dim3 grid((e.B + SK_TGT_LANES - 1) / SK_TGT_LANES), block(SK_TGT_LANES);
+  switch (L.N) {
+    case 2: hipLaunchKernelGGL(k_rollout_targets<2>, grid, block, 0, (hipStream_t)stream, a); break;
+    case 3: hipLaunchKernelGGL(k_rollout_targets<3>, grid, block, 0, (hipStream_t)stream, a); break;
+    case 4: hipLaunchKernelGGL(k_rollout_targets<4>, grid, block, 0, (hipStream_t)stream, a); break;
+    default: hipLaunchKernelGGL(k_rollout_targets<0>, grid, block, 0, (hipStream_t)stream, a); break;
+  }
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+// ---- learner minibatches of a rollout buffer (include/skyjo_vec.h: skyjo_vec_rollout_select / _gather; the kernels: skyjo_batches.h) ----
+int skyjo_vec_rollout_select(skyjo_vec *h, const uint8_t *flags, int64_t n_rows, int32_t require_bits, const float *advantages,
+                             int64_t *index_out, int64_t *count_out, double *moments_out, void *stream) {
+  if (!h || !flags || !index_out || !count_out) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_select: null argument");
+  if ((advantages == nullptr) != (moments_out == nullptr))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_select: advantages and moments_out go together");
+  if (n_rows < 0 || n_rows > (int64_t)SK_SEL_ROWS * 0x7fffffff) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_select: n_rows out of range");
+  if (require_bits < 1 || require_bits > 255) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_select: require_bits must lie in 1 .. 255");
+  const SkEngineView e = sk_engine_view(h);
+  DevGuard guard_(e.device_id);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t nb = (size_t)((n_rows + SK_SEL_ROWS - 1) / SK_SEL_ROWS);
+  void *scratch = nullptr;
+  size_t cap = 0;
+  if (int rc = sk_engine_select_scratch(h, nb, &scratch, &cap)) return rc;
+  long long *counts = (long long *)scratch;
+  double *sums = (double *)(counts + cap);
+  if (nb) {
+    hipLaunchKernelGGL(k_select_pass<false>, dim3((unsigned)nb), dim3(SK_SEL_THREADS), 0, s, flags, (long long)n_rows, (uint32_t)require_bits,
+                       advantages, counts, sums, (long long *)nullptr);
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(SK_SCAN_THREADS), 0, s, counts, (const double *)sums, (int)nb, (long long *)count_out, moments_out);
+  HIPCHK(hipGetLastError());
+  if (nb) {
+    hipLaunchKernelGGL(k_select_pass<true>, dim3((unsigned)nb), dim3(SK_SEL_THREADS), 0, s, flags, (long long)n_rows, (uint32_t)require_bits,
+                       (const float *)nullptr, counts, sums, (long long *)index_out);
+    HIPCHK(hipGetLastError());
+  }
+  return SKYJO_OK;
+}
+
+int skyjo_vec_rollout_gather(skyjo_vec *h, const void *records, int32_t layout, int32_t T, const int64_t *index, int64_t m,
+                             const int32_t *actions, const float *logp, const float *values, int32_t value_stride, const float *advantages,
+                             const float *value_targets, float adv_mean, float adv_std, float *obs_out, float *logmask_out,
+                             int64_t *actions_out, float *logp_out, float *advantages_out, float *value_targets_out, float *values_out,
+                             uint8_t *seats_out, void *stream) {
+  if (!h || !records || !index || !actions || !logp || !values || !advantages || !value_targets || !obs_out || !logmask_out ||
+      !actions_out || !logp_out || !advantages_out || !value_targets_out || !values_out || !seats_out)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather: null argument");
+  if (m < 0 || T < 1 || value_stride < 1) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather: m must not be negative, T and value_stride at least 1");
+  if (int rc = check_layout(layout)) return rc;
+  if (!std::isfinite(adv_mean) || !std::isfinite(adv_std) || !(adv_std > 0.f))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather: adv_mean must be finite, adv_std finite and greater than 0");
+  if ((((uintptr_t)records | (uintptr_t)obs_out | (uintptr_t)logmask_out) & 15) != 0)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather: records, obs_out and logmask_out must be 16-byte aligned");
+  if (m == 0) return SKYJO_OK;
+  const SkEngineView e = sk_engine_view(h);
+  DevGuard guard_(e.device_id);
+  const SkLayout &L = *e.L;
+  static_assert(SK_GATHER_MAX_PIECES * 16 >= ((19 + 12 * SKYJO_MAX_PLAYERS + 3) & ~3) + 32, "the largest record fits k_gather_rows' LDS image");
+  SkGatherArgs a{};
+  a.rec = (const uint8_t *)records, a.index = (const long long *)index, a.actions = actions, a.logp = logp, a.values = values;
+  a.adv = advantages, a.vt = value_targets;
+  a.obs_out = obs_out, a.lm_out = logmask_out, a.act_out = (long long *)actions_out, a.logp_out = logp_out, a.adv_out = advantages_out;
+  a.vt_out = value_targets_out, a.val_out = values_out, a.seat_out = seats_out;
+  a.planar = layout == SKYJO_REC_TILE_PLANAR;
+  a.m = m, a.n_rows = (long long)T * e.B, a.rec_stride = a.planar ? (long long)e.G : (long long)e.B;
+  a.B = e.B, a.vstride = value_stride, a.rec_bytes = L.rec_bytes, a.D = L.D, a.Dp = L.Dp;
+  a.mean = adv_mean, a.std = adv_std;
+  hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((m + SK_GATHER_ROWS - 1) / SK_GATHER_ROWS)), dim3(SK_GATHER_THREADS), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+// ---- the PPO loss head of a learner minibatch (include/skyjo_vec.h: skyjo_vec_ppo_loss; the kernels: skyjo_loss.h) ----
+static constexpr int64_t kLossMaxRows = (int64_t)SK_LOSS_ROWS * 0x7fffffff;
+int64_t skyjo_vec_ppo_loss_scratch_bytes(int64_t m) {
+  if (m < 1 || m > kLossMaxRows) return 0;
+  return (m + SK_LOSS_ROWS - 1) / SK_LOSS_ROWS * (int64_t)(SK_LOSS_STATS * sizeof(double));
+}
+
+int skyjo_vec_ppo_loss(const float *logits, const float *log_mask, const float *value, const int64_t *actions, const float *logp_old,
+                       const float *advantages, const float *value_targets, const float *values_old, int64_t m, float clip,
+                       float vf_coef, float ent_coef, float vf_clip, float *grad_logits_out, float *grad_value_out, double *stats_out,
+                       void *scratch, int64_t scratch_bytes, void *stream) {
+  if (!logits || !log_mask || !value || !actions || !logp_old || !advantages || !value_targets || !values_old || !grad_logits_out ||
+      !grad_value_out || !stats_out || !scratch)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: null argument");
+  if (m < 1 || m > kLossMaxRows) return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: m must be at least 1");
+  if (!std::isfinite(clip) || !(clip > 0.f)) return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: clip must be finite and greater than 0");
+  if (!std::isfinite(vf_coef) || !std::isfinite(ent_coef)) return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: vf_coef and ent_coef must be finite");
+  if ((((uintptr_t)logits | (uintptr_t)log_mask | (uintptr_t)grad_logits_out) & 15) != 0)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: logits, log_mask and grad_logits_out must be 16-byte aligned");
+  if ((((uintptr_t)value | (uintptr_t)logp_old | (uintptr_t)advantages | (uintptr_t)value_targets | (uintptr_t)values_old |
+        (uintptr_t)grad_value_out) & 3) != 0 || (((uintptr_t)actions | (uintptr_t)stats_out | (uintptr_t)scratch) & 7) != 0)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: a column, stats_out or scratch is not aligned to its element size");
+  if (scratch_bytes < skyjo_vec_ppo_loss_scratch_bytes(m)) return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: scratch is smaller than skyjo_vec_ppo_loss_scratch_bytes(m)");
+  static_assert(SK_LOSS_ROWS % 2 == 0 && SK_LOSS_ROWS <= SK_LOSS_THREADS, "a run is whole 16-byte pieces and every row has its lane");
+  SkLossArgs a{};
+  a.logits = logits, a.log_mask = log_mask, a.value = value, a.actions = (const long long *)actions, a.logp_old = logp_old;
+  a.adv = advantages, a.vt = value_targets, a.v_old = values_old, a.g_logits = grad_logits_out, a.g_value = grad_value_out;
+  a.partial = (double *)scratch, a.m = m;
+  a.lo = (float)(1.0 - (double)clip), a.hi = (float)(1.0 + (double)clip);
+  a.vf_coef = vf_coef, a.ent_coef = ent_coef;
+  a.vf_clip = (std::isfinite(vf_clip) && vf_clip > 0.f) ? vf_clip : 0.f;
+  a.inv_m = 1.0f / (float)m;
+  const int64_t nb = (m + SK_LOSS_ROWS - 1) / SK_LOSS_ROWS;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_ppo_loss, dim3((unsigned)nb), dim3(SK_LOSS_THREADS), 0, s, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_ppo_loss_finish, dim3(1), dim3(SK_LOSS_FIN_THREADS), 0, s, (const double *)scratch, (int)nb, (double)m, stats_out);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// skyjo_loss.h - part of skyjo_device.h's family (included from skyjo_capi.hip after skyjo_batches.h: it reduces with sk_wave_sum).
+// skyjo_loss.h - learner kernels (included from skyjo_learner.hip after skyjo_batches.h: they reduce with sk_wave_sum).
 // The PPO loss head of a learner minibatch: from the policy branch's raw logits, the log-mask and the value output to the loss, its
 // statistics and the gradients with respect to the logits and the value - what stands between a model's two outputs and
 // optimizer.step().  include/skyjo_vec.h (skyjo_vec_ppo_loss) and DESIGN.md 4 have the definition; tests/ppo_loss_ref.py restates it.
@@ -15,9 +15,10 @@
 //     order (k_select_scan's order), divided by m: stats[0 .. 5] = loss, policy_loss, vf_loss, entropy, kl, clip_fraction.
 //     The same input gives the same bits on every call.
 #pragma once
-#ifndef SKYJO_DEVICE_PARTS
-#error "include skyjo_device.h first"
-#endif
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/skyjo_vec.h"
 
 #define SK_LOSS_ROWS 128     // even: a run's byte length (rows * 104) is a multiple of 16
 #define SK_LOSS_THREADS 128  // one lane per row

@@ -1,4 +1,4 @@
-// skyjo_policy.h - what the C ABI (skyjo_capi.hip) and the policy net's translation unit (skyjo_policy.hip) share: the
+// skyjo_policy.h - what the C ABI (skyjo_capi.hip, skyjo_learner.hip) and the policy net's translation unit (skyjo_policy.hip) share: the
 // packed-net descriptor, the draw descriptor and the one host entry point that launches the net kernels.  The kernels
 // live in a translation unit of their own so that each side gets the instruction scheduler that suits it (the
 // environment kernels gain 1 - 2 % under `-amdgpu-sched-strategy=max-ilp`, the net kernels lose 18 %: EXPERIMENTS r5 #11).

@@ -1,5 +1,5 @@
-// skyjo_targets.h - part of skyjo_device.h's family (included from skyjo_capi.hip after skyjo_device.h: it reads records through
-// sk_rec_byte of skyjo_callers.h).  Learner targets of a rollout buffer: per-seat GAE(gamma, lambda), one lane per game.
+// skyjo_targets.h - a learner kernel (included from skyjo_learner.hip; it reads records through sk_rec_byte of skyjo_layout.h and is no
+// part of the environment's sources).  Learner targets of a rollout buffer: per-seat GAE(gamma, lambda), one lane per game.
 //
 // What RLlib's PPO computes per agent trajectory for the sample batches of the reference's trainer
 // (rlskyjo/models/train_model_simple_rllib.py:22-59: `advantages`, `value_targets`) - here over the columns
@@ -18,9 +18,10 @@
 // Two to four seats keep their carries in registers, selected by compares; the generic form (one seat, five to twelve) keeps
 // them in lane-private LDS columns and reads the rare reward row where the chain meets it.  No instantiation has a private segment.
 #pragma once
-#ifndef SKYJO_DEVICE_PARTS
-#error "include skyjo_device.h first"
-#endif
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "skyjo_layout.h"
 
 #define SK_TGT_BLOCK 16  // time steps whose inputs are in flight together
 #define SK_TGT_LANES 64  // one wavefront per workgroup: 65 536 games = one wavefront per SIMD

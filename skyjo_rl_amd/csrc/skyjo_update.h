@@ -1,4 +1,4 @@
-// skyjo_update.h - included from skyjo_capi.hip after skyjo_policy.h (it uses SKP_*).  The packed net's layout, stated once, and the
+// skyjo_update.h - included from skyjo_learner.hip after skyjo_policy.h (it uses SKP_*).  The packed net's layout, stated once, and the
 // kernel that writes an existing skyjo_vec_mlp's blob in place from device memory: skyjo_vec_mlp_update (repack) and
 // skyjo_vec_mlp_adam_step (torch.optim.Adam's rule in front of the pack).  include/skyjo_vec.h and DESIGN.md 4 have the definition;
 // tests/mlp_pack_ref.py restates the layout.
