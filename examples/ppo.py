@@ -12,7 +12,7 @@ import torch
 
 from skyjo_rl_amd._lib import TGT_HAS_TARGET
 from skyjo_rl_amd.action_mask_model import FLOAT_MIN, FusedNet
-from skyjo_rl_amd.learner import STATS, PPOLossBuffers, ppo_loss
+from skyjo_rl_amd.learner import STATS, NativeBranch, PPOLossBuffers, ppo_loss
 from skyjo_rl_amd.rollout import compute_targets, minibatches, select_rows
 
 
@@ -94,8 +94,38 @@ def _ppo_update_native_loss(model, buf, optimizer, epochs, minibatch, clip, vf_c
     return {"first": stats[0], "last": stats[-1], "transitions": sel.count}
 
 
+def _ppo_update_native_nets(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip):
+    """``ppo_update(..., native_batches=True, native_loss=True, native_nets=True)``: the two branches as well - per minibatch gather,
+    two forwards, the loss head, two backwards and the optimizer's step, every one a native call (``learner.NativeBranch``): no autograd
+    graph, no allocation inside the loop, no ``zero_grad`` (``backward`` overwrites the gradients)."""
+    compute_targets(buf, gamma=gae[0], lam=gae[1])
+    sel = select_rows(buf, TGT_HAS_TARGET)
+    norm = (sel.mean, max(sel.std, 1e-6))
+    gen = torch.Generator(device=buf.actions.device).manual_seed(seed)
+    rows = max(min(minibatch, sel.count), 1)
+    out = PPOLossBuffers(rows, buf.actions.device)
+    policy, value_branch = NativeBranch(model.policy, rows), NativeBranch(model.value, rows)
+    stats = []
+    for ep in range(epochs):
+        tot = torch.zeros((6,), dtype=torch.float64, device=buf.actions.device)
+        seen = 0
+        for mb in minibatches(buf, minibatch, generator=gen, normalize=norm, selection=sel):
+            logits = policy.forward(mb.observations)  # (the kernel adds the mask: action_mask_model.py:70-71)
+            value = value_branch.forward(mb.observations)
+            res = ppo_loss(logits, value, mb, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, vf_clip=vf_clip, out=out)
+            policy.backward(res.grad_logits)
+            value_branch.backward(res.grad_value)
+            optimizer.step()
+            n = mb.actions.numel()
+            tot += res.stats * n
+            seen += n
+        host = (tot / max(seen, 1)).tolist()  # the epoch's one read
+        stats.append({k: host[STATS.index(k)] for k in ("policy_loss", "vf_loss", "kl", "entropy", "clip_fraction")})
+    return {"first": stats[0], "last": stats[-1], "transitions": sel.count}
+
+
 def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_coef=1.0, seed=0, gae=None, native_batches=False,
-               native_loss=False, ent_coef=0.0, vf_clip=None):
+               native_loss=False, ent_coef=0.0, vf_clip=None, native_nets=False):
     """Clipped-surrogate PPO epochs over the buffer (RLlib defaults: clip_param 0.3, vf_loss_coeff 1.0).  Returns the mean
     losses of the first and the last epoch.  ``gae``: None - Monte-Carlo returns of the episodes that ended inside the buffer
     (``compute_returns``); (gamma, lambda) - advantages, value targets and the row mask of ``rollout.compute_targets`` (one
@@ -104,12 +134,17 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
     on the buffer as it lies, no ``buf.views()`` - instead of the torch expressions below.  ``native_loss`` (needs
     ``native_batches``): the loss head is ``learner.ppo_loss`` - one kernel between the model's outputs and ``optimizer.step()``; only
     this path knows ``ent_coef`` (an entropy bonus) and ``vf_clip`` (RLlib's ``vf_clip_param``), and its statistics gain ``entropy``
-    and ``clip_fraction``."""
+    and ``clip_fraction``.  ``native_nets`` (needs ``native_loss``): the two branches' forwards and backwards are
+    ``learner.NativeBranch``'s kernels on the float32 parameters - a minibatch step is then a fixed sequence of native launches."""
+    if native_nets and not native_loss:
+        raise ValueError("native_nets=True needs native_loss=True")
     if native_loss:
         if not native_batches:
             raise ValueError("native_loss=True needs native_batches=True")
         if gae is None:
             raise ValueError("native_batches=True needs gae=(gamma, lambda)")
+        if native_nets:
+            return _ppo_update_native_nets(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip)
         return _ppo_update_native_loss(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip)
     if ent_coef != 0.0 or vf_clip is not None:
         raise ValueError("ent_coef and vf_clip belong to native_loss=True")

@@ -539,6 +539,39 @@ int skyjo_vec_ppo_loss(const float *logits, const float *log_mask, const float *
                        float vf_coef, float ent_coef, float vf_clip, float *grad_logits_out, float *grad_value_out,
                        double *stats_out /* device, 6 */, void *scratch, int64_t scratch_bytes, void *stream);
 
+/* One branch of the model - Linear(obs_dim, 256) - tanh - Linear(256, 256) - tanh - Linear(256, out_dim), 1 <= obs_dim <= 31,
+ * 1 <= out_dim <= 32: skyjo_vec_mlp_create's limits - trained on its float32 master parameters, on device: the forward that keeps its
+ * activations and the backward that reads them, what torch's autograd otherwise does between a minibatch and the loss head and between
+ * the loss head and the optimizer.  Needs no handle: the calls run on the current device, on `stream`.  Every product runs on the exact
+ * float32 matrix instruction (float32 in, float32 accumulate: an fmaf chain), not on the packed nets' bf16 pairs; tanh is tanhf.
+ *   params[i] / grads[i]  w1, b1, w2, b2, w3, b3 in torch.nn.Linear layout - [256][obs_dim], [256], [256][256], [256], [out_dim][256],
+ *                         [out_dim] - the order of skyjo_vec_mlp_adam_step; w2 and w3 16-byte aligned.  grads are OVERWRITTEN
+ *   x                     float32 [m][obs_dim], dense (obs_out of skyjo_vec_rollout_gather);  m >= 1
+ *   out / grad_out        float32 [m][out_dim]: the branch's output, and the gradient of the loss with respect to it
+ *   workspace             caller-owned, 16-byte aligned, at least skyjo_vec_mlp_train_workspace_bytes(obs_dim, out_dim, m) bytes.  Floats:
+ *                         h1 [m][256], h2 [m][256], dz2 [m][256], dz1 [m][256], then one record of 82 208 per chunk of 256 rows
+ *                         (ceil(m / 256) chunks): dW2 [256][256], dW1 [256][32] (column k >= obs_dim unused but 31, which is db1),
+ *                         dW3 [32][256] (rows >= out_dim unused), db2 [256], db3 [32]
+ * skyjo_vec_mlp_train_forward:  h1 = tanh(x W1^T + b1), h2 = tanh(h1 W2^T + b2), out = h2 W3^T + b3, one kernel, 64 rows per workgroup;
+ * h1 and h2 - the values the next layer consumed - stay in the workspace.  A sum over k runs in one float32 chain: layer 1 over
+ * x padded to 32 columns with a 1 in column 31 against b1 (so b1 is the chain's term k = 31), layers 2 and 3 from 0 with the bias added
+ * to the finished sum; within every group of 8 consecutive k the order is k0, k0 + 4, k0 + 1, k0 + 5, k0 + 2, k0 + 6, k0 + 3, k0 + 7.
+ * skyjo_vec_mlp_train_backward: reads the activations which the FORWARD OF THE SAME (params, x, m) LEFT IN THE SAME WORKSPACE - nothing
+ * is recomputed and nothing checks it - and runs three kernels.  Rows: dz2 = (g W3) (1 - h2 h2), dz1 = (dz2 W2) (1 - h1 h1), chains
+ * over k as above (over out_dim: ascending).  Weights: dW3 = g^T h2, dW2 = dz2^T h1, dW1 = dz1^T x and the column sums db3, db2, db1 of
+ * g, dz2, dz1, per chunk of 256 rows: one chain over the chunk's rows, ascending, for a weight (db1 as the column of ones in the padded
+ * x), runs of 64 (db2) or 32 (db3) rows added in order for the other biases.  Finish: an element's chunk partials are added in double,
+ * chunk 0 first, and rounded to float32 once.  No chain over rows is longer than 256, no atomics: the same input gives the same bits
+ * on every call.  Rows beyond m of the last tile and chunk enter as zeros and are never read or written.
+ * SKYJO_E_INVALID (nothing is launched): a null pointer (an element of params or grads included), m < 1, obs_dim or out_dim out of
+ * range, a workspace that is too small, w2 / w3 / workspace not 16-byte aligned. */
+int64_t skyjo_vec_mlp_train_workspace_bytes(int32_t obs_dim, int32_t out_dim, int64_t m); /* 0 for invalid arguments */
+int skyjo_vec_mlp_train_forward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, int64_t m,
+                                float *out /* [m][out_dim] */, void *workspace, int64_t workspace_bytes, void *stream);
+int skyjo_vec_mlp_train_backward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x,
+                                 const float *grad_out /* [m][out_dim] */, int64_t m, float *const grads[6] /* overwritten */,
+                                 void *workspace, int64_t workspace_bytes, void *stream);
+
 /* host-pointer conveniences for small batches (single-game AEC view): synchronous.  Up to 4096 games they go through
  * host-mapped memory (one launch + one synchronisation per call, no copies), and step_host / reset_host bring every game's
  * state and rewards back with the records: skyjo_vec_get_state and skyjo_vec_get_rewards_host right after them cost no

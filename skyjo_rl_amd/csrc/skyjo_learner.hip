@@ -1,6 +1,6 @@
 // skyjo_learner.hip - the packed nets' handles and the learner behind the extern "C" boundary of include/skyjo_vec.h: skyjo_vec_mlp_*,
-// skyjo_vec_rollout_targets / _select / _gather and skyjo_vec_ppo_loss, with their kernels (skyjo_update.h, skyjo_targets.h,
-// skyjo_batches.h, skyjo_loss.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
+// skyjo_vec_rollout_targets / _select / _gather, skyjo_vec_ppo_loss and skyjo_vec_mlp_train_*, with their kernels (skyjo_update.h,
+// skyjo_targets.h, skyjo_batches.h, skyjo_loss.h, skyjo_train.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
 // (skyjo_capi.hip, skyjo_device.h and its parts), and of an engine it sees what skyjo_host.h shows - the record layout, B, G, game_id0,
 // the device and the select scratch.  gfx950 only, no CPU path.
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 #include "skyjo_targets.h"
 #include "skyjo_batches.h"
 #include "skyjo_loss.h"
+#include "skyjo_train.h"
 
 extern "C" {
 
@@ -337,6 +338,82 @@ int skyjo_vec_ppo_loss(const float *logits, const float *log_mask, const float *
   hipLaunchKernelGGL(k_ppo_loss, dim3((unsigned)nb), dim3(SK_LOSS_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_ppo_loss_finish, dim3(1), dim3(SK_LOSS_FIN_THREADS), 0, s, (const double *)scratch, (int)nb, (double)m, stats_out);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+// ---- a branch's training forward and backward on its float32 parameters (include/skyjo_vec.h: skyjo_vec_mlp_train_*; skyjo_train.h) ----
+namespace {
+
+constexpr int64_t kTrainMaxRows = (int64_t)1 << 30;
+int64_t train_chunks(int64_t m) { return (m + SKT_CHUNK_ROWS - 1) / SKT_CHUNK_ROWS; }
+
+// the checks the two calls share and the workspace's views; 0 or the code fail() returned
+int train_args(const char *who, int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, int64_t m, void *workspace,
+               int64_t workspace_bytes, SkTrainArgs &a) {
+  const std::string name(who);
+  if (!params || !x || !workspace) return fail(SKYJO_E_INVALID, name + ": null argument");
+  for (int i = 0; i < 6; i++)
+    if (!params[i]) return fail(SKYJO_E_INVALID, name + ": null parameter");
+  if (obs_dim < 1 || obs_dim > SKT_IN - 1 || out_dim < 1 || out_dim > SKT_OUT)
+    return fail(SKYJO_E_INVALID, name + ": obs_dim must be 1..31 and out_dim 1..32");
+  if (m < 1 || m > kTrainMaxRows) return fail(SKYJO_E_INVALID, name + ": m must be at least 1");
+  if (workspace_bytes < skyjo_vec_mlp_train_workspace_bytes(obs_dim, out_dim, m))
+    return fail(SKYJO_E_INVALID, name + ": workspace is smaller than skyjo_vec_mlp_train_workspace_bytes");
+  if (!aligned16(params[2]) || !aligned16(params[4]) || !aligned16(workspace))
+    return fail(SKYJO_E_INVALID, name + ": w2, w3 and workspace must be 16-byte aligned");
+  for (int i = 0; i < 6; i++)
+    if ((uintptr_t)params[i] & 3) return fail(SKYJO_E_INVALID, name + ": a parameter is not aligned to its element size");
+  if ((uintptr_t)x & 3) return fail(SKYJO_E_INVALID, name + ": x is not aligned to its element size");
+  a.w1 = params[0], a.b1 = params[1], a.w2 = params[2], a.b2 = params[3], a.w3 = params[4], a.b3 = params[5];
+  a.x = x, a.m = m, a.D = obs_dim, a.O = out_dim, a.chunks = (int)train_chunks(m);
+  const size_t act = (size_t)m * SKT_H;
+  a.h1 = (float *)workspace, a.h2 = a.h1 + act, a.dz2 = a.h2 + act, a.dz1 = a.dz2 + act, a.part = a.dz1 + act;
+  return SKYJO_OK;
+}
+
+}  // namespace
+
+int64_t skyjo_vec_mlp_train_workspace_bytes(int32_t obs_dim, int32_t out_dim, int64_t m) {
+  if (obs_dim < 1 || obs_dim > SKT_IN - 1 || out_dim < 1 || out_dim > SKT_OUT || m < 1 || m > kTrainMaxRows) return 0;
+  return (int64_t)sizeof(float) * (4 * m * SKT_H + train_chunks(m) * SKT_PART);
+}
+
+int skyjo_vec_mlp_train_forward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, int64_t m, float *out,
+                                void *workspace, int64_t workspace_bytes, void *stream) {
+  static const char *who = "skyjo_vec_mlp_train_forward";
+  SkTrainArgs a{};
+  if (!out) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
+  if (int rc = train_args(who, obs_dim, out_dim, params, x, m, workspace, workspace_bytes, a)) return rc;
+  if ((uintptr_t)out & 3) return fail(SKYJO_E_INVALID, std::string(who) + ": out is not aligned to its element size");
+  a.out = out;
+  const unsigned tiles = (unsigned)((m + SKT_TILE_ROWS - 1) / SKT_TILE_ROWS);
+  hipLaunchKernelGGL(k_mlp_train_fwd, dim3(tiles), dim3(SKT_THREADS), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+int skyjo_vec_mlp_train_backward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, const float *grad_out,
+                                 int64_t m, float *const grads[6], void *workspace, int64_t workspace_bytes, void *stream) {
+  static const char *who = "skyjo_vec_mlp_train_backward";
+  SkTrainArgs a{};
+  if (!grad_out || !grads) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
+  for (int i = 0; i < 6; i++)
+    if (!grads[i]) return fail(SKYJO_E_INVALID, std::string(who) + ": null gradient");
+  if (int rc = train_args(who, obs_dim, out_dim, params, x, m, workspace, workspace_bytes, a)) return rc;
+  if ((uintptr_t)grad_out & 3) return fail(SKYJO_E_INVALID, std::string(who) + ": grad_out is not aligned to its element size");
+  for (int i = 0; i < 6; i++) {
+    if ((uintptr_t)grads[i] & 3) return fail(SKYJO_E_INVALID, std::string(who) + ": a gradient is not aligned to its element size");
+    a.grads[i] = grads[i];
+  }
+  a.g = grad_out;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned tiles = (unsigned)((m + SKT_TILE_ROWS - 1) / SKT_TILE_ROWS);
+  hipLaunchKernelGGL(k_mlp_train_bwd_rows, dim3(tiles), dim3(SKT_THREADS), 0, s, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_mlp_train_bwd_weights, dim3((unsigned)a.chunks, SKT_SLICES), dim3(SKT_THREADS), 0, s, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_mlp_train_bwd_finish, dim3((SKT_PART + SKT_THREADS - 1) / SKT_THREADS), dim3(SKT_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
   return SKYJO_OK;
 }

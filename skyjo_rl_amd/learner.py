@@ -3,7 +3,9 @@ and returns the PPO loss, its statistics and the gradients with respect to both 
 reduction (``skyjo_vec_ppo_loss``, csrc/skyjo_loss.h) instead of the chain of small torch expressions and their autograd twins that
 otherwise stands between the model and ``optimizer.step()``.  ``PPOLoss`` wraps it as a ``torch.autograd.Function``.  ``NativeAdam`` is the
 step itself: Adam fused with the re-pack of the updated weights into the ``FusedNet``s' MFMA fragments, in place (``skyjo_vec_mlp_adam_step``,
-csrc/skyjo_update.h) - the rollout that follows needs no new nets.
+csrc/skyjo_update.h) - the rollout that follows needs no new nets.  ``NativeBranch`` is what remains in between: one branch's forward,
+which keeps its activations, and its backward on the float32 master parameters (``skyjo_vec_mlp_train_forward`` / ``_backward``,
+csrc/skyjo_train.h: the exact float32 matrix instruction, no autograd graph, no allocation per step).
 
 The definition (include/skyjo_vec.h has it in full): the masked softmax of ``action_mask_model.py:58-74`` - logits plus
 the log-mask - the clipped surrogate, the squared value error and the entropy of the PPO the reference trains with
@@ -28,6 +30,9 @@ from . import _lib
 PPOLossResult = namedtuple("PPOLossResult", ["stats", "grad_logits", "grad_value"])
 STATS = ("loss", "policy_loss", "vf_loss", "entropy", "kl", "clip_fraction")  # the order of ``PPOLossResult.stats``
 NUM_ACTIONS = 26
+HIDDEN = 256
+TRAIN_TILE_ROWS = 64     # SKT_TILE_ROWS of csrc/skyjo_train.h: the rows of a workgroup in the forward and the backward's row pass
+TRAIN_CHUNK_ROWS = 256   # SKT_CHUNK_ROWS: the rows of one partial of the weight gradients - the longest chain over rows
 
 
 class PPOLossBuffers:
@@ -168,3 +173,118 @@ class NativeAdam:
                 _lib.check(self._L.skyjo_vec_mlp_adam_step(net._h, pp, gg, buf.data_ptr(), buf.numel() * 4, float(self.lr), self.betas[0],
                                                            self.betas[1], self.eps, self.steps + 1, torch.cuda.current_stream().cuda_stream))
         self.steps += 1
+
+
+class _BranchFunction(torch.autograd.Function):
+    """``NativeBranch.apply``: the branch's two native calls as one autograd node over (x, w1, b1, w2, b2, w3, b3)."""
+
+    @staticmethod
+    def forward(ctx, branch, x, *params):
+        out = branch.forward(x.detach())
+        ctx.branch, ctx.call = branch, branch._call  # (the workspace's identity: nothing else is saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        branch = ctx.branch
+        if branch._call != ctx.call:
+            raise RuntimeError("this NativeBranch ran another forward since: its workspace holds that call's activations")
+        branch._backward(grad_out.contiguous())
+        return (None, None) + tuple(g.clone() if need else None for g, need in zip(branch.grads, ctx.needs_input_grad[2:]))
+
+
+class NativeBranch:
+    """One branch of the model (``model.policy`` or ``model.value``: Linear-Tanh-Linear-Tanh-Linear, 256 hidden units) trained by
+    native calls on its float32 parameters as they lie: ``forward(x)`` is ONE kernel that leaves h1 and h2 in this object's workspace,
+    ``backward(grad_out)`` three more - the row pass, the weight pass over chunks of ``TRAIN_CHUNK_ROWS`` rows and the fixed-order sum
+    of the chunks' partials (include/skyjo_vec.h: ``skyjo_vec_mlp_train_*``).  The workspace, the output buffer and the six gradient
+    tensors (``grads``: w1, b1, w2, b2, w3, b3) are allocated here, once, for up to ``max_rows`` rows; a step allocates nothing, builds no
+    autograd graph and does not synchronise.  The same input gives the same bits on every call.
+
+    ``seq`` is checked with ``FusedNet.branch_parameters``' rules - three ``nn.Linear`` of shapes [256, D], [256, 256], [O, 256] with
+    1 <= D <= 31 and 1 <= O <= 32, contiguous float32 on one GPU - at construction and again at every call (a parameter that was
+    replaced by one of another shape or device is a ``ValueError``, not a launch)."""
+
+    def __init__(self, seq, max_rows):
+        self._L = _lib.load()
+        self._lins = [m for m in seq if isinstance(m, torch.nn.Linear)]
+        if len(self._lins) != 3:
+            raise ValueError("seq must hold three nn.Linear")
+        w1, w3 = self._lins[0].weight, self._lins[2].weight
+        if not isinstance(w1, torch.Tensor) or w1.dim() != 2 or not isinstance(w3, torch.Tensor) or w3.dim() != 2:
+            raise ValueError("seq's linears must have two-dimensional weights")
+        self.obs_dim, self.out_dim, self.device = int(w1.shape[1]), int(w3.shape[0]), w1.device
+        if self.device.type != "cuda":
+            raise ValueError("NativeBranch runs on the GPU: the parameters are on " + str(self.device))
+        if not (1 <= self.obs_dim <= 31 and 1 <= self.out_dim <= 32):
+            raise ValueError("the branch must have 1..31 inputs and 1..32 outputs")
+        if max_rows < 1:
+            raise ValueError("max_rows must be at least 1")
+        self.max_rows = int(max_rows)
+        params = self.parameters()
+        nbytes = int(self._L.skyjo_vec_mlp_train_workspace_bytes(self.obs_dim, self.out_dim, self.max_rows))
+        if nbytes <= 0:
+            raise ValueError("max_rows is out of range")
+        self.workspace = torch.empty((nbytes // 4,), dtype=torch.float32, device=self.device)
+        self.out = torch.empty((self.max_rows, self.out_dim), dtype=torch.float32, device=self.device)
+        self.grads = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in params]
+        self._gg = (C.c_void_p * 6)(*[g.data_ptr() for g in self.grads])
+        self._x, self._call = None, 0
+
+    def parameters(self):
+        """w1, b1, w2, b2, w3, b3 of ``seq`` as they are now, checked."""
+        shapes = ((HIDDEN, self.obs_dim), (HIDDEN,), (HIDDEN, HIDDEN), (HIDDEN,), (self.out_dim, HIDDEN), (self.out_dim,))
+        names = ("0.weight", "0.bias", "1.weight", "1.bias", "2.weight", "2.bias")
+        params = [t for lin in self._lins for t in (lin.weight, lin.bias)]
+        for name, t, shape in zip(names, params, shapes):
+            _column("linear " + name, t, torch.float32, shape, self.device)
+        if params[2].data_ptr() % 16 or params[4].data_ptr() % 16:
+            raise ValueError("linear 1.weight and 2.weight must start on a 16-byte boundary")
+        return params
+
+    @torch.no_grad()
+    def forward(self, x):
+        """``x`` float32 [m, D], contiguous on the branch's GPU, 1 <= m <= ``max_rows``.  Returns the branch's output float32 [m, O]: a
+        view of ``out``, valid until the next ``forward``.  ``x`` is kept (not copied) for ``backward``."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or not 1 <= x.shape[0] <= self.max_rows:
+            raise ValueError(f"x must be a float32 tensor of shape [m, {self.obs_dim}], 1 <= m <= {self.max_rows}")
+        m = int(x.shape[0])
+        _column("x", x, torch.float32, (m, self.obs_dim), self.device)
+        pp = (C.c_void_p * 6)(*[p.data_ptr() for p in self.parameters()])
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.skyjo_vec_mlp_train_forward(self.obs_dim, self.out_dim, pp, x.data_ptr(), m, self.out.data_ptr(),
+                                                           self.workspace.data_ptr(), self.workspace.numel() * 4,
+                                                           torch.cuda.current_stream().cuda_stream))
+        self._x, self._call = x, self._call + 1
+        return self.out[:m]
+
+    def _backward(self, grad_out):
+        if self._x is None:
+            raise ValueError("backward needs a forward first: the workspace holds no activations")
+        m = int(self._x.shape[0])
+        if not isinstance(grad_out, torch.Tensor) or grad_out.dim() != 2 or grad_out.shape[0] != m:
+            raise ValueError(f"grad_out must have the {m} rows of the last forward")
+        _column("grad_out", grad_out, torch.float32, (m, self.out_dim), self.device)
+        params = self.parameters()
+        pp = (C.c_void_p * 6)(*[p.data_ptr() for p in params])
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.skyjo_vec_mlp_train_backward(self.obs_dim, self.out_dim, pp, self._x.data_ptr(), grad_out.data_ptr(), m,
+                                                            self._gg, self.workspace.data_ptr(), self.workspace.numel() * 4,
+                                                            torch.cuda.current_stream().cuda_stream))
+        return params
+
+    @torch.no_grad()
+    def backward(self, grad_out):
+        """``grad_out`` float32 [m, O] - the gradient with respect to what the last ``forward`` returned, m its row count (anything
+        else is a ``ValueError``, as is a call before the first ``forward``).  Overwrites ``grads`` with the gradients of the six
+        parameters and makes them the parameters' ``.grad`` - whatever ``zero_grad(set_to_none=True)`` did before; ``NativeAdam.step()``
+        or a torch optimizer's reads them there.  Reads the parameters and the ``x`` of that ``forward``: both must be unchanged."""
+        for p, g in zip(self._backward(grad_out), self.grads):
+            p.grad = g
+
+    def apply(self, x):
+        """The same pair inside autograd, ``torch.autograd.Function`` over (x, the six parameters): returns ``forward(x)`` with a
+        graph node whose backward runs ``backward``'s kernels and hands CLONES of ``grads`` to autograd - which accumulates them into
+        ``.grad`` as it does for any function, so a torch-side loss composes with it.  ``x`` gets no gradient.  Backward after another
+        ``forward`` of this object raises ``RuntimeError``: the activations are gone."""
+        return _BranchFunction.apply(self, x, *self.parameters())
