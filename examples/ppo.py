@@ -202,3 +202,21 @@ def repack(model, device=0):
     existing net from the parameters on the GPU in one launch, and ``learner.NativeAdam(model, pol, val, lr=...)`` passed to
     ``ppo_update`` as its ``optimizer`` does that inside every ``step()`` - the nets a rollout holds then never change identity."""
     return FusedNet(model.policy, device=device), FusedNet(model.value, device=device)
+
+
+def evaluate_vs_random(env, policy_net, T, seat=0, seed=0, first_ticket=0):
+    """Did training help?  ``policy_net`` (the ``FusedNet`` of the trained policy branch) plays GREEDY - ``logits.argmax()`` over the
+    legal actions, what ``rlskyjo/models/train_model_simple_rllib.py:123-130`` does with its trained policies - in seat ``seat``, and
+    ``policy_ra`` (uniform over the legal actions) plays every other seat, for ``T`` lockstep iterations of ``env`` in one native call
+    (``skyjo_rl_amd.arena``).  Returns ``arena.EpisodeStats``: episodes, and per seat the mean / standard deviation of the final reward
+    and the win rate; ``stats.mean_reward[seat]`` and ``stats.win_rate[seat]`` are the trained seat's.
+
+    The rewards of the training rollout cannot answer the question.  A seat's final reward is ``-score + mean(scores) + mean_reward``
+    (plus the refund bonus; skyjo_env.py:293-312): relative to the table's mean.  In self-play with one shared policy the seats'
+    rewards therefore average to ``mean_reward`` per episode whatever the policy has learned - a better policy lowers every seat's
+    score and the mean with it.  Against seats that stay random, the trained seat's reward and win rate move with its skill."""
+    from skyjo_rl_amd import arena
+
+    seats = ["random"] * env.num_players
+    seats[seat] = ("greedy", policy_net)
+    return arena.evaluate(env, seats, T, seed=seed, first_ticket=first_ticket)

@@ -572,6 +572,66 @@ int skyjo_vec_mlp_train_backward(int32_t obs_dim, int32_t out_dim, const float *
                                  const float *grad_out /* [m][out_dim] */, int64_t m, float *const grads[6] /* overwritten */,
                                  void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Arena rollouts: the evaluation path beside skyjo_vec_model_rollout.  Every SEAT has a policy of its own - what the reference's script
+ * does when it trains one policy per seat (rlskyjo/models/train_model_simple_rllib.py:43-49) and afterwards plays them with
+ * logits.argmax() (:123-130) - and a seat may play policy_ra instead (rlskyjo/models/random_admissible_policy.py:26-28).  In self-play
+ * with one shared policy the seats' final rewards are relative to the table's mean (skyjo_env.py:293-312) and average to mean_reward
+ * whatever the policy learns; a trained seat against random seats is what shows progress.
+ *
+ * seats: num_players entries, seat s = the policy of the player the record's agent byte calls s.  Seats that share a `net` pointer share
+ * one forward.  skyjo_vec_arena_select, one lockstep iteration's actions: every distinct net gets ONE launch of the net kernel (no draw)
+ * over all num_envs records into its slice of the workspace - as many full-batch net launches as there are distinct nets; games are not
+ * compacted by seat - and ONE more kernel, one lane per game, takes the game's agent byte and mask out of the record (either layout),
+ * the seat's kind and the seat's net's row, and writes actions_out[g]:
+ *   SKYJO_SEAT_SAMPLE  the draw of skyjo_vec_sample_actions with (seed, ticket, game_id0 + g) on the seat's net's logits: the bits of
+ *                      skyjo_vec_mlp_forward_layout + skyjo_vec_sample_actions_layout, hence of skyjo_vec_mlp_act
+ *   SKYJO_SEAT_GREEDY  the smallest k that maximises m[k], m[k] = logits[k] + (legal ? 0 : FLOAT_MIN) in float32 - the m the draw forms;
+ *                      no random number is used
+ *   SKYJO_SEAT_RANDOM  SKYJO_SEAT_SAMPLE on 26 zero logits: uniform over the legal actions; `net` must be NULL
+ * The action is defined for every game; a game whose record already shows `done` has it ignored by the step, as in the training rollout.
+ *   workspace  device memory of the caller, 16-byte aligned, at least skyjo_vec_arena_workspace_bytes(h, number of distinct nets) bytes:
+ *              per distinct net float32 [num_envs][26], rounded up to a multiple of 16 bytes.  With no net at all (every seat
+ *              SKYJO_SEAT_RANDOM) it may be NULL / 0.
+ * skyjo_vec_arena_rollout: T lockstep iterations of  [the net forwards] -> [the select kernel] -> [skyjo_vec_step_collect]  on one
+ * stream, nothing on the host in between, nothing read back.  buffers as for skyjo_vec_model_rollout - records[0] in, records[1 .. T],
+ * actions, final_rewards and episode_end out, in the layout the engine's step writes (SKYJO_OPT_RECORD_LAYOUT) - but logp and values
+ * must be NULL, and final_rewards / episode_end are required.  Iteration t draws with ticket first_ticket + t: with every seat
+ * SKYJO_SEAT_SAMPLE on one net these are the bits of skyjo_vec_model_rollout.
+ * (An engine that was never seeded is refused by the first skyjo_vec_step_collect with SKYJO_E_STATE; that iteration's actions are
+ * computed by then, the engine is untouched.)
+ * SKYJO_E_INVALID (nothing is launched): a null pointer, T < 1, an unknown kind, a net with SKYJO_SEAT_RANDOM or none without it, a net
+ * whose out_dim is not 26, whose obs_dim is not the engine's or that lives on another device, a workspace that is too small or not
+ * 16-byte aligned, logp or values set, a layout that is neither SKYJO_REC_ROW_MAJOR nor SKYJO_REC_TILE_PLANAR. */
+#define SKYJO_SEAT_SAMPLE 0
+#define SKYJO_SEAT_GREEDY 1
+#define SKYJO_SEAT_RANDOM 2
+typedef struct skyjo_vec_seat_policy {
+  const skyjo_vec_mlp *net; /* NULL iff kind == SKYJO_SEAT_RANDOM */
+  int32_t kind;             /* SKYJO_SEAT_* */
+  int32_t reserved;
+} skyjo_vec_seat_policy;
+int64_t skyjo_vec_arena_workspace_bytes(const skyjo_vec *h, int32_t distinct_nets); /* 0 for NULL or distinct_nets outside 0 .. 12 */
+int skyjo_vec_arena_select(skyjo_vec *h, const skyjo_vec_seat_policy *seats /* [num_players] */, const void *records, int32_t layout,
+                           uint64_t seed, uint64_t ticket, int32_t *actions_out /* [num_envs] */, void *workspace,
+                           int64_t workspace_bytes, void *stream);
+int skyjo_vec_arena_rollout(skyjo_vec *h, const skyjo_vec_seat_policy *seats /* [num_players] */, int32_t T, uint64_t seed,
+                            uint64_t first_ticket, const skyjo_vec_rollout_buffers *buffers /* logp and values must be NULL */,
+                            void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Per-seat results of the episodes that ended inside a buffer: over the rows = T * num_envs rows of its final_rewards (double
+ * [rows][num_players]) and episode_end (uint8 [rows]) columns, one kernel plus a single-workgroup reduction, all in double, in a fixed
+ * order, without atomics - the same input gives the same bits on every call.  Needs no handle: it runs on the current device, on `stream`.
+ *   stats_out  double [1 + 3 num_players] (device): [0] the number of rows with episode_end != 0; then per seat s
+ *              [1 + 3 s] the sum of the seat's final reward over those rows, [2 + 3 s] the sum of its squares (each square rounded
+ *              once), [3 + 3 s] the number of those rows in which the seat's reward equals the row's maximum over the seats (a tie counts
+ *              for every tied seat).  All 0 when no row ended an episode.  final_rewards is read only where episode_end is set.
+ *   scratch    caller-owned, 8-byte aligned, at least skyjo_vec_episode_stats_scratch_bytes(rows, num_players) bytes
+ * SKYJO_E_INVALID (nothing is launched): a null pointer, rows < 1, num_players outside 1 .. 12, a misaligned array, a scratch that is
+ * too small. */
+int64_t skyjo_vec_episode_stats_scratch_bytes(int64_t rows, int32_t num_players); /* 0 for invalid arguments */
+int skyjo_vec_episode_stats(const double *final_rewards, const uint8_t *episode_end, int64_t rows, int32_t num_players,
+                            double *stats_out /* device, 1 + 3 num_players */, void *scratch, int64_t scratch_bytes, void *stream);
+
 /* host-pointer conveniences for small batches (single-game AEC view): synchronous.  Up to 4096 games they go through
  * host-mapped memory (one launch + one synchronisation per call, no copies), and step_host / reset_host bring every game's
  * state and rewards back with the records: skyjo_vec_get_state and skyjo_vec_get_rewards_host right after them cost no

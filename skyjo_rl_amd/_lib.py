@@ -72,6 +72,12 @@ class RolloutBuffers(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("records", "actions", "logp", "values", "final_rewards", "episode_end")]
 
 
+class SeatPolicy(C.Structure):  # skyjo_vec_seat_policy
+    _fields_ = [("net", C.c_void_p), ("kind", C.c_int32), ("reserved", C.c_int32)]
+
+
+SEAT_SAMPLE, SEAT_GREEDY, SEAT_RANDOM = 0, 1, 2  # SKYJO_SEAT_*
+
 # option ids / record layouts of include/skyjo_vec.h
 OPT_RECORD_LAYOUT, REC_ROW_MAJOR, REC_TILE_PLANAR, REC_TILE_PLANAR_ALL = 6, 0, 1, 2
 TGT_HAS_TARGET, TGT_EPISODE_KNOWN = 1, 2  # SKYJO_TGT_*: bits of skyjo_vec_rollout_targets' flags column
@@ -121,6 +127,11 @@ SIGNATURES = {
     "skyjo_vec_mlp_train_workspace_bytes": (I64, [I32, I32, I64]),
     "skyjo_vec_mlp_train_forward": (C.c_int, [I32, I32, VP, VP, I64, VP, VP, I64, VP]),
     "skyjo_vec_mlp_train_backward": (C.c_int, [I32, I32, VP, VP, VP, I64, VP, VP, I64, VP]),
+    "skyjo_vec_arena_workspace_bytes": (I64, [VP, I32]),
+    "skyjo_vec_arena_select": (C.c_int, [VP, C.POINTER(SeatPolicy), VP, I32, U64, U64, VP, VP, I64, VP]),
+    "skyjo_vec_arena_rollout": (C.c_int, [VP, C.POINTER(SeatPolicy), I32, U64, U64, C.POINTER(RolloutBuffers), VP, I64, VP]),
+    "skyjo_vec_episode_stats_scratch_bytes": (I64, [I64, I32]),
+    "skyjo_vec_episode_stats": (C.c_int, [VP, VP, I64, I32, VP, VP, I64, VP]),
     "skyjo_vec_rewards_ptr": (VP, [VP]),
     "skyjo_vec_scores_ptr": (VP, [VP]),
     "skyjo_vec_done_ptr": (VP, [VP]),

@@ -1,0 +1,172 @@
+"""Arena rollouts: every SEAT plays a policy of its own, and the episodes that end become per-seat results.
+
+The training rollout (``rollout.collect``) drives all seats with one net, sampled.  That cannot say whether training helped: a seat's
+final reward is relative to the table's mean (skyjo_env.py:293-312), so with one shared policy the seats' rewards average to
+``mean_reward`` whatever the policy has learned.  The reference's own script trains one policy per seat
+(``rlskyjo/models/train_model_simple_rllib.py:43-49``) and afterwards plays the trained policies with ``logits.argmax()``
+(``:123-130``).  This module is that evaluation path, beside the training rollout and not inside it: per lockstep iteration ONE
+full-batch launch of the net kernel per DISTINCT net, one small kernel that gives every game the action of the seat whose turn it is,
+and the engine's ``skyjo_vec_step_collect`` - ``skyjo_vec_arena_rollout`` runs T such iterations in one native call.
+
+A seat is ``("sample", net)`` - the masked categorical draw of the training rollout -, ``("greedy", net)`` - the argmax of the masked
+logits, the smallest index on a tie - or ``"random"`` - ``policy_ra``, uniform over the legal actions.  ``net`` is a ``FusedNet`` of a
+model's policy branch; seats that hold the same ``FusedNet`` share its forward.  ``episode_stats`` turns the ``final_rewards`` /
+``episode_end`` columns of a played buffer into episodes, mean and standard deviation of the final reward and win rate per seat
+(``skyjo_vec_episode_stats``).
+"""
+import ctypes as C
+import math
+from collections import namedtuple
+
+from . import _lib
+
+KINDS = {"sample": _lib.SEAT_SAMPLE, "greedy": _lib.SEAT_GREEDY, "random": _lib.SEAT_RANDOM}
+
+EpisodeStats = namedtuple("EpisodeStats", ["episodes", "mean_reward", "std_reward", "win_rate"])
+
+
+def seat_policies(env, seats):
+    """The ctypes array ``skyjo_vec_seat_policy[num_players]`` for ``seats``: a list of ``env.num_players`` entries, each
+    ``("sample", FusedNet)``, ``("greedy", FusedNet)`` or ``"random"``.  The array keeps its nets alive (``.nets``: the distinct ones,
+    in the order of their first seat).  ``ValueError`` for a wrong length, an unknown kind, a closed net, a missing net or a net
+    combined with ``"random"``."""
+    seats = list(seats)
+    if len(seats) != env.num_players:
+        raise ValueError(f"seats has {len(seats)} entries, the engine has {env.num_players} players")
+    arr = (_lib.SeatPolicy * len(seats))()
+    nets = []
+    for s, entry in enumerate(seats):
+        kind, net = None, None
+        if isinstance(entry, str):
+            kind = entry
+        elif isinstance(entry, (tuple, list)) and len(entry) in (1, 2) and isinstance(entry[0], str):
+            kind, net = entry[0], entry[1] if len(entry) == 2 else None
+        if kind not in KINDS:
+            raise ValueError(f"seat {s}: {entry!r} is not ('sample', net), ('greedy', net) or 'random'")
+        if kind == "random":
+            if net is not None:
+                raise ValueError(f"seat {s}: 'random' takes no net")
+        else:
+            handle = getattr(net, "_h", None)
+            if net is None or not hasattr(net, "_h"):
+                raise ValueError(f"seat {s}: '{kind}' needs a FusedNet")
+            if not handle:
+                raise ValueError(f"seat {s}: this FusedNet is closed")
+            if not any(n is net for n in nets):
+                nets.append(net)
+            arr[s].net = handle.value if isinstance(handle, C.c_void_p) else handle
+        arr[s].kind = KINDS[kind]
+    arr.nets = nets
+    return arr
+
+
+def _seats(env, seats):
+    return seats if isinstance(seats, C.Array) and getattr(seats, "_type_", None) is _lib.SeatPolicy else seat_policies(env, seats)
+
+
+def _workspace(env, holder, sp):
+    """(pointer, bytes) of a workspace for ``sp``'s distinct nets, cached on ``holder``; (None, 0) when no seat has a net."""
+    distinct = len({s.net for s in sp if s.net})
+    need = int(_lib.load().skyjo_vec_arena_workspace_bytes(env._h, distinct))
+    if need == 0:
+        return None, 0
+    ws = getattr(holder, "_arena_workspace", None)
+    if ws is None or ws.numel() < need:
+        torch = env._torch()
+        ws = torch.empty((need,), dtype=torch.uint8, device=env._dev())
+        holder._arena_workspace = ws
+    return C.c_void_p(ws.data_ptr()), ws.numel()
+
+
+def select(env, seats, records, seed=0, ticket=0, actions=None, planar=False, workspace=None):
+    """One lockstep iteration's actions (``skyjo_vec_arena_select``): int32 [num_envs] for ``env.step``, the action of the seat each
+    game's record expects.  ``records``: one iteration's records of ``env`` - [num_envs, record_bytes], or with ``planar`` one
+    tile-planar block [tiles, P, 64, 16], read in place.  ``seats``: as for ``seat_policies`` (or its result).  ``workspace``: an
+    object to cache the logits' workspace on (default: the seat array)."""
+    torch = env._torch()
+    sp = _seats(env, seats)
+    want = (env.tiles * 64 if planar else env.num_envs) * env.record_bytes
+    if not records.is_contiguous() or records.numel() != want or records.dtype != torch.uint8:
+        raise ValueError(f"records must be one iteration's contiguous uint8 records ({want} bytes with planar={planar})")
+    if actions is None:
+        actions = torch.empty((env.num_envs,), dtype=torch.int32, device=env._dev())
+    elif actions.dtype != torch.int32 or actions.numel() != env.num_envs or not actions.is_contiguous():
+        raise ValueError("actions must be a contiguous int32 tensor of num_envs elements")
+    ws, nbytes = _workspace(env, sp if workspace is None else workspace, sp)
+    _lib.check(_lib.load().skyjo_vec_arena_select(env._h, sp, C.c_void_p(records.data_ptr()), _lib.REC_TILE_PLANAR if planar else _lib.REC_ROW_MAJOR,
+                                                  int(seed), int(ticket), C.c_void_p(actions.data_ptr()), ws, nbytes, env._stream()))
+    return actions
+
+
+def play(env, seats, buf, seed=0, first_ticket=0, first_records=None):
+    """Fill ``buf`` (a ``rollout.RolloutBuffer`` of ``env``) with T lockstep iterations of the seats' policies in one native call
+    (``skyjo_vec_arena_rollout``): ``records``, ``actions``, ``final_rewards`` and ``episode_end`` as ``rollout.collect`` lays them
+    out; ``buf.logp`` and ``buf.values`` are left as they are.  Either record layout: ``buf.planar`` must be what the engine writes.
+    Iteration t draws with ticket ``first_ticket + t``; ``first_records``: the records to start from (default: ``env.observe()``).
+    The logits' workspace is cached on the buffer."""
+    from . import rollout
+
+    rollout._check_records(buf)
+    if buf.planar != (env.record_layout == "tile-planar-all"):
+        raise ValueError(f"buf.planar={buf.planar}, but the engine's record layout is {env.record_layout!r}")
+    if buf.B != env.num_envs or buf.N != env.num_players:
+        raise ValueError("buf was made for another engine shape")
+    sp = _seats(env, seats)
+    ws, nbytes = _workspace(env, buf, sp)
+    rollout._first(env, buf, first_records)
+    vp = lambda t: t.data_ptr()
+    b = _lib.RolloutBuffers(vp(buf.records), vp(buf.actions), None, None, vp(buf.final_rewards), vp(buf.episode_end))
+    _lib.check(_lib.load().skyjo_vec_arena_rollout(env._h, sp, buf.T, int(seed), int(first_ticket), C.byref(b), ws, nbytes, env._stream()))
+    return buf
+
+
+def stats_from_sums(sums, num_players):
+    """``EpisodeStats`` from the ``1 + 3 N`` doubles of ``skyjo_vec_episode_stats`` (the count, then per seat sum, sum of squares,
+    wins), the moments taken in double: ``std`` is the unbiased estimate and 0.0 for fewer than two episodes."""
+    n = int(sums[0])
+    mean, std, win = [], [], []
+    for s in range(num_players):
+        x, q, w = (float(v) for v in sums[1 + 3 * s: 4 + 3 * s])
+        mean.append(x / n if n else 0.0)
+        std.append(math.sqrt(max(q - x * x / n, 0.0) / (n - 1)) if n > 1 else 0.0)
+        win.append(w / n if n else 0.0)
+    return EpisodeStats(n, tuple(mean), tuple(std), tuple(win))
+
+
+def episode_stats(buf):
+    """Per-seat results of the episodes that ended inside a filled buffer: ``EpisodeStats(episodes, mean_reward, std_reward,
+    win_rate)`` - the number of rows with ``episode_end``, and per seat (tuples of ``num_players`` floats) the mean and the unbiased
+    standard deviation of its final reward over them and the fraction in which it holds the table's highest reward (a tie counts for
+    every tied seat).  One native call on the buffer's columns (``skyjo_vec_episode_stats``: sums in double, fixed order); the copy
+    of its ``1 + 3 N`` doubles to the host is the only synchronisation."""
+    import torch
+
+    L = _lib.load()
+    fr, ee = buf.final_rewards, buf.episode_end
+    N = fr.shape[-1]
+    rows = ee.numel()
+    if fr.dtype != torch.float64 or ee.dtype != torch.uint8 or fr.numel() != rows * N or not fr.is_contiguous() or not ee.is_contiguous():
+        raise ValueError("final_rewards must be contiguous float64 [..., N] and episode_end contiguous uint8 with the same leading shape")
+    need = int(L.skyjo_vec_episode_stats_scratch_bytes(rows, N))
+    out = getattr(buf, "_stats_out", None)
+    if out is None or out.numel() < 1 + 3 * N + need // 8:
+        out = torch.empty((1 + 3 * N + need // 8,), dtype=torch.float64, device=fr.device)  # the sums, then the scratch
+        try:
+            buf._stats_out = out
+        except AttributeError:
+            pass
+    with torch.cuda.device(fr.device):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(L.skyjo_vec_episode_stats(C.c_void_p(fr.data_ptr()), C.c_void_p(ee.data_ptr()), rows, N, C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(out[1 + 3 * N:].data_ptr()), need, stream))
+        host = out[: 1 + 3 * N].cpu()
+    return stats_from_sums(host.tolist(), N)
+
+
+def evaluate(env, seats, T, seed=0, first_ticket=0, first_records=None):
+    """``play`` for T iterations on a buffer of its own, then ``episode_stats``."""
+    from . import rollout
+
+    buf = rollout.RolloutBuffer(env, T)
+    play(env, seats, buf, seed=seed, first_ticket=first_ticket, first_records=first_records)
+    return episode_stats(buf)

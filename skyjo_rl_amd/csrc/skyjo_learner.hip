@@ -1,6 +1,6 @@
 // skyjo_learner.hip - the packed nets' handles and the learner behind the extern "C" boundary of include/skyjo_vec.h: skyjo_vec_mlp_*,
-// skyjo_vec_rollout_targets / _select / _gather, skyjo_vec_ppo_loss and skyjo_vec_mlp_train_*, with their kernels (skyjo_update.h,
-// skyjo_targets.h, skyjo_batches.h, skyjo_loss.h, skyjo_train.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
+// skyjo_vec_rollout_targets / _select / _gather, skyjo_vec_ppo_loss, skyjo_vec_mlp_train_*, skyjo_vec_arena_* and skyjo_vec_episode_stats,
+// with their kernels (skyjo_update.h, skyjo_targets.h, skyjo_batches.h, skyjo_loss.h, skyjo_train.h, skyjo_arena.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
 // (skyjo_capi.hip, skyjo_device.h and its parts), and of an engine it sees what skyjo_host.h shows - the record layout, B, G, game_id0,
 // the device and the select scratch.  gfx950 only, no CPU path.
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 #include "skyjo_batches.h"
 #include "skyjo_loss.h"
 #include "skyjo_train.h"
+#include "skyjo_arena.h"
 
 extern "C" {
 
@@ -414,6 +415,137 @@ int skyjo_vec_mlp_train_backward(int32_t obs_dim, int32_t out_dim, const float *
   hipLaunchKernelGGL(k_mlp_train_bwd_weights, dim3((unsigned)a.chunks, SKT_SLICES), dim3(SKT_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_mlp_train_bwd_finish, dim3((SKT_PART + SKT_THREADS - 1) / SKT_THREADS), dim3(SKT_THREADS), 0, s, a);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+// ---- arena rollouts: a policy per seat, and the episode-end columns as per-seat results (include/skyjo_vec.h: skyjo_vec_arena_*,
+// skyjo_vec_episode_stats; the kernels: skyjo_arena.h).  The engine is stepped through the public skyjo_vec_step_collect. ----
+namespace {
+
+struct ArenaPlan {
+  SkArenaArgs a{};
+  const skyjo_vec_mlp *net[SKYJO_MAX_PLAYERS] = {};  // the distinct nets, in the order of their first seat
+  SkEngineView e{};
+};
+
+// the seats checked against the engine, the distinct nets and the workspace; 0 or the code fail() returned
+int arena_plan(const char *who, const skyjo_vec *h, const skyjo_vec_seat_policy *seats, const void *workspace, int64_t workspace_bytes, ArenaPlan &p) {
+  const std::string name(who);
+  if (!h || !seats) return fail(SKYJO_E_INVALID, name + ": null argument");
+  p.e = sk_engine_view(h);
+  const SkLayout &L = *p.e.L;
+  static_assert(SKYJO_MAX_PLAYERS <= 16, "a seat's net is a 4-bit field of SkArenaArgs::seat_net, its kind a 2-bit field of ::kinds");
+  SkArenaArgs &a = p.a;
+  for (int s = 0; s < L.N; s++) {
+    const skyjo_vec_mlp *m = seats[s].net;
+    const int32_t kind = seats[s].kind;
+    if (kind != SKYJO_SEAT_SAMPLE && kind != SKYJO_SEAT_GREEDY && kind != SKYJO_SEAT_RANDOM) return fail(SKYJO_E_INVALID, name + ": unknown seat kind");
+    if (kind == SKYJO_SEAT_RANDOM) {
+      if (m) return fail(SKYJO_E_INVALID, name + ": a SKYJO_SEAT_RANDOM seat takes no net");
+    } else {
+      if (!m) return fail(SKYJO_E_INVALID, name + ": a SKYJO_SEAT_SAMPLE or SKYJO_SEAT_GREEDY seat needs a net");
+      if (m->net.out_dim != SKYJO_NUM_ACTIONS) return fail(SKYJO_E_INVALID, name + ": a seat's net needs 26 outputs");
+      if (m->device_id != p.e.device_id || m->obs_dim != L.D)
+        return fail(SKYJO_E_INVALID, name + ": a seat's net must live on the engine's device and take the engine's observation");
+      int j = 0;
+      while (j < a.nets && p.net[j] != m) j++;
+      if (j == a.nets) p.net[a.nets++] = m;
+      a.seat_net |= (uint64_t)j << (4 * s);
+    }
+    a.kinds |= (uint32_t)kind << (2 * s);
+  }
+  if (a.nets) {
+    if (!workspace) return fail(SKYJO_E_INVALID, name + ": seats with nets need a workspace");
+    if ((uintptr_t)workspace & 15) return fail(SKYJO_E_INVALID, name + ": workspace must be 16-byte aligned");
+    if (workspace_bytes < skyjo_vec_arena_workspace_bytes(h, a.nets))
+      return fail(SKYJO_E_INVALID, name + ": workspace is smaller than skyjo_vec_arena_workspace_bytes");
+    a.logits = (const float *)workspace;
+  }
+  a.n = p.e.B, a.game_id0 = p.e.game_id0, a.Dp = L.Dp, a.rec_bytes = L.rec_bytes, a.N = L.N;
+  return SKYJO_OK;
+}
+
+// one lockstep iteration's actions: a full-batch forward per distinct net, then ONE k_arena_select
+int arena_launch(const ArenaPlan &p, const uint8_t *rec, int planar, uint64_t seed, uint64_t ticket, int32_t *actions, hipStream_t s) {
+  SkArenaArgs a = p.a;
+  a.rec = rec, a.planar = planar, a.seed = seed, a.ticket = ticket, a.actions = actions;
+  const SkMlpDraw nodraw{};
+  for (int j = 0; j < a.nets; j++)
+    if (int rc = launch_mlp(p.net[j], p.net[j], 1, rec, (int)a.rec_bytes, p.net[j]->obs_dim, (int64_t)a.n,
+                            const_cast<float *>(a.logits) + (size_t)j * sk_arena_slice(a.n), nodraw, nullptr, s, planar))
+      return rc;
+  hipLaunchKernelGGL(k_arena_select, dim3((unsigned)((a.n + SK_ARENA_BLOCK - 1) / SK_ARENA_BLOCK)), dim3(SK_ARENA_BLOCK), 0, s, a);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+constexpr int64_t kStatMaxRows = (int64_t)SK_STAT_ROWS << 30;
+
+}  // namespace
+
+int64_t skyjo_vec_arena_workspace_bytes(const skyjo_vec *h, int32_t distinct_nets) {
+  if (!h || distinct_nets < 0 || distinct_nets > SKYJO_MAX_PLAYERS) return 0;
+  return (int64_t)distinct_nets * sk_arena_slice(sk_engine_view(h).B) * (int64_t)sizeof(float);
+}
+
+int skyjo_vec_arena_select(skyjo_vec *h, const skyjo_vec_seat_policy *seats, const void *records, int32_t layout, uint64_t seed, uint64_t ticket,
+                           int32_t *actions_out, void *workspace, int64_t workspace_bytes, void *stream) {
+  static const char *who = "skyjo_vec_arena_select";
+  if (!records || !actions_out) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
+  if (int rc = check_layout(layout)) return rc;
+  ArenaPlan p;
+  if (int rc = arena_plan(who, h, seats, workspace, workspace_bytes, p)) return rc;
+  DevGuard guard_(p.e.device_id);
+  return arena_launch(p, (const uint8_t *)records, (int)(layout == SKYJO_REC_TILE_PLANAR), seed, ticket, actions_out, (hipStream_t)stream);
+}
+
+int skyjo_vec_arena_rollout(skyjo_vec *h, const skyjo_vec_seat_policy *seats, int32_t T, uint64_t seed, uint64_t first_ticket,
+                            const skyjo_vec_rollout_buffers *b, void *workspace, int64_t workspace_bytes, void *stream) {
+  static const char *who = "skyjo_vec_arena_rollout";
+  if (!b || !b->records || !b->actions || !b->final_rewards || !b->episode_end) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
+  if (b->logp || b->values) return fail(SKYJO_E_INVALID, std::string(who) + ": logp and values must be NULL (the arena writes neither)");
+  if (T < 1) return fail(SKYJO_E_INVALID, std::string(who) + ": T must be at least 1");
+  ArenaPlan p;
+  if (int rc = arena_plan(who, h, seats, workspace, workspace_bytes, p)) return rc;
+  int64_t lay = 0;  // what skyjo_vec_step_collect writes: tile-planar records with SKYJO_REC_TILE_PLANAR_ALL, row-major otherwise
+  if (int rc = skyjo_vec_get_option(h, SKYJO_OPT_RECORD_LAYOUT, &lay)) return rc;
+  const int planar = lay == SKYJO_REC_TILE_PLANAR_ALL;
+  const size_t B = (size_t)p.e.B, N = (size_t)p.e.L->N, per_it = (planar ? p.e.G : B) * (size_t)p.e.L->rec_bytes;
+  uint8_t *rec = (uint8_t *)b->records;
+  for (int t = 0; t < T; t++) {
+    int32_t *act = b->actions + (size_t)t * B;
+    {
+      DevGuard guard_(p.e.device_id);
+      if (int rc = arena_launch(p, rec + (size_t)t * per_it, planar, seed, first_ticket + (uint64_t)t, act, (hipStream_t)stream)) return rc;
+    }
+    if (int rc = skyjo_vec_step_collect(h, act, rec + (size_t)(t + 1) * per_it, b->final_rewards + (size_t)t * B * N, b->episode_end + (size_t)t * B, stream))
+      return rc;
+  }
+  return SKYJO_OK;
+}
+
+int64_t skyjo_vec_episode_stats_scratch_bytes(int64_t rows, int32_t num_players) {
+  if (rows < 1 || rows > kStatMaxRows || num_players < 1 || num_players > SKYJO_MAX_PLAYERS) return 0;
+  return (rows + SK_STAT_ROWS - 1) / SK_STAT_ROWS * (int64_t)((1 + 3 * num_players) * sizeof(double));
+}
+
+int skyjo_vec_episode_stats(const double *final_rewards, const uint8_t *episode_end, int64_t rows, int32_t num_players, double *stats_out,
+                            void *scratch, int64_t scratch_bytes, void *stream) {
+  static const char *who = "skyjo_vec_episode_stats";
+  if (!final_rewards || !episode_end || !stats_out || !scratch) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
+  if (rows < 1 || rows > kStatMaxRows) return fail(SKYJO_E_INVALID, std::string(who) + ": rows must be at least 1");
+  if (num_players < 1 || num_players > SKYJO_MAX_PLAYERS) return fail(SKYJO_E_INVALID, std::string(who) + ": num_players must lie in 1 .. 12");
+  if ((((uintptr_t)final_rewards | (uintptr_t)stats_out | (uintptr_t)scratch) & 7) != 0)
+    return fail(SKYJO_E_INVALID, std::string(who) + ": final_rewards, stats_out and scratch must be 8-byte aligned");
+  if (scratch_bytes < skyjo_vec_episode_stats_scratch_bytes(rows, num_players))
+    return fail(SKYJO_E_INVALID, std::string(who) + ": scratch is smaller than skyjo_vec_episode_stats_scratch_bytes");
+  const int64_t nb = (rows + SK_STAT_ROWS - 1) / SK_STAT_ROWS;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_episode_stats, dim3((unsigned)nb), dim3(SK_STAT_THREADS), 0, s, final_rewards, episode_end, (long long)rows, (int)num_players,
+                     (double *)scratch);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_episode_stats_finish, dim3(1), dim3(SK_STAT_FIN_THREADS), 0, s, (const double *)scratch, (int)nb, (int)num_players, stats_out);
   HIPCHK(hipGetLastError());
   return SKYJO_OK;
 }
