@@ -315,7 +315,11 @@ int skyjo_vec_get_option(const skyjo_vec *h, int option, int64_t *value_out);
  *   logits     float32 [n][26]  the policy net's outputs (device)
  *   records    [n][record_bytes] as written by step / reset / observe / rollout (device)
  *   seed, ticket   the uniform of game i is word 0 of Philox4x32-10(counter = (ticket, game_id0 + i, 0x53414D50),
- *              key = seed): the same (seed, ticket) reproduces the same draws; advance ticket once per step
+ *              key = seed): the same (seed, ticket) reproduces the same draws; advance ticket once per step.
+ *              Word by word, with gid = game_id0 + i as a 64-bit sum (it wraps) and M = 0xffffffff:
+ *                counter = (ticket & M, ticket >> 32, gid & M, 0x53414D50 ^ (gid >> 32)),  key = (seed & M, seed >> 32);
+ *              uniform = (float)(word 0 >> 8) * 2^-24, 24 bits in [0, 1).  tests/net_ref.py restates it, tests/test_net_ref.py
+ *              holds the restatement to Random123's published vectors and tests/test_gpu_net_synthetic.py the kernel to it.
  *   no_masking != 0: the mask is ignored (action_mask_model.py:53-56,66-67)
  *   actions_out int32 [n]; logp_out float32 [n] (log-probability of the drawn action) or NULL;
  *   uniform_out float32 [n] (the uniforms in [0, 1), for tests) or NULL.
