@@ -105,11 +105,18 @@ class FusedNet:
     def __call__(self, records, out=None, planar=False):
         """Outputs float32 [n, out_dim] for the records' games.  ``planar``: ``records`` is tile-planar ([..., tiles, P, 64, 16], what
         ``SkyjoVecEnv.rollout`` writes with ``set_record_layout("tile-planar")``), read in place; n = 64 x the number of blocks
-        (the rows beyond ``num_envs`` of a partial last tile are computed from whatever the block holds)."""
+        (the rows beyond ``num_envs`` of a partial last tile are computed from whatever the block holds: of several iterations
+        [iters, tiles, P, 64, 16] row ``(it * tiles) * 64 + g`` is game g of iteration it).  ``out`` of a planar input: all 64 x blocks rows -
+        or, for ONE iteration's blocks, the first ``out.shape[0]`` games (the output tells the game count).  ``ValueError`` for
+        several iterations with any other ``out``: iters x num_envs rows would be filled as if the padding slots were games."""
         rb = int(records.shape[-3] * 16) if planar else int(records.shape[-1])
         n = records.numel() // rb
         if out is not None:  # (planar blocks are whole tiles: the caller's output says how many games there are)
-            n = min(n, out.numel() // self.out_dim)
+            rows = out.numel() // self.out_dim
+            if planar and rows != n and (rows > n or records.numel() != records.shape[-4:].numel()):
+                raise ValueError(f"out holds {rows} rows, the tile-planar records {n} (64 x {n // 64} blocks): fewer rows than that are "
+                                 "taken for the first games of ONE iteration's blocks only")
+            n = min(n, rows)
         if out is None:
             out = torch.empty((n, self.out_dim), dtype=torch.float32, device=records.device)
         C = self._C

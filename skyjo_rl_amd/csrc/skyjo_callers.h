@@ -47,10 +47,13 @@ __global__ __launch_bounds__(SK_SAMPLE_BLOCK) void k_sample(SkLayout L, const ui
 __global__ void k_episode_ends(SkParams P, const uint8_t *rec, double *rew_out, uint8_t *end_out, int planar) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= P.B) return;
-  const uint8_t *meta = sk_rec_byte(rec, g, P.L.Dp + 26, P.L.rec_bytes, planar);  // agent, phase, done, status (one 4-byte word)
+  // The done byte, Dp + 28, with a sk_rec_byte call of its own, never as an offset from the agent byte: agent, phase, done and status
+  // start at Dp + 26, which is 2 mod 4, and for the direct observation with 4, 8 or 12 players 14 mod 16 - done then lies in the
+  // next 16-byte piece, 1 KiB further on in the tile-planar layout.
+  const uint8_t done = *sk_rec_byte(rec, g, P.L.Dp + 28, P.L.rec_bytes, planar);
   // done, and the step that wrote the record applied (or refused) an action: byte D is -1 for a game that was re-dealt,
   // already over or left alone (SKYJO_ACTION_SKIP) - none of those ends an episode (again)
-  const bool end = meta[2] != 0 && (int8_t)*sk_rec_byte(rec, g, P.L.D, P.L.rec_bytes, planar) != -1;
+  const bool end = done != 0 && (int8_t)*sk_rec_byte(rec, g, P.L.D, P.L.rec_bytes, planar) != -1;
   end_out[g] = end ? 1 : 0;
   for (int p = 0; p < P.L.N; p++) rew_out[(size_t)g * P.L.N + p] = end ? P.rewards[(size_t)g * P.L.N + p] : 0.0;
 }

@@ -53,7 +53,20 @@ class RolloutBuffer:
         return self.views().done[: self.T] == 0
 
 
+def _check_handoff(env, buf):
+    """``buf.planar`` is captured when the buffer is made, the engine reads its layout when it is called, and the native calls take no
+    size: a buffer of the other layout would be overrun (num_envs % 64 != 0) or silently filled in the other layout."""
+    if buf.planar != (env.record_layout == "tile-planar-all"):
+        raise ValueError(f"buf.planar={buf.planar}, but the engine's record layout is {env.record_layout!r}")
+    want = (buf.T + 1) * (env.tiles * 64 if buf.planar else env.num_envs) * env.record_bytes
+    r = buf.records
+    if r.dtype != torch.uint8 or not r.is_contiguous() or r.numel() != want:
+        raise ValueError(f"buf.records must be contiguous uint8 of {want} bytes (T + 1 = {buf.T + 1} iterations, planar={buf.planar}), "
+                         f"not {r.numel()} of shape {tuple(r.shape)}")
+
+
 def _first(env, buf, first_records):
+    _check_handoff(env, buf)
     if first_records is None:
         env.observe(out=buf.records[0])
     else:

@@ -138,6 +138,18 @@ class SkyjoVecEnv:
         """One iteration's records in the layout ``reset`` / ``observe`` / ``step`` write."""
         return self.new_planar_records() if self.record_layout == "tile-planar-all" else self.new_records()
 
+    def _step_records(self, out):
+        """``out`` of ``reset`` / ``observe`` / ``step``: a new tensor, or the caller's - checked, because the native call takes no size
+        and writes (tiles * 64 with 'tile-planar-all', num_envs otherwise) * record_bytes bytes whatever it is given."""
+        if out is None:
+            return self._new_step_records()
+        torch = self._torch()
+        slots = self.tiles * 64 if self.record_layout == "tile-planar-all" else self.num_envs
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != slots * self.record_bytes:
+            raise ValueError(f"out must be a contiguous uint8 tensor of {slots} x {self.record_bytes} bytes: one iteration's records "
+                             f"in the engine's layout ({self.record_layout!r})")
+        return out
+
     def new_planar_records(self, *iters):
         return self._torch().empty((*iters, self.tiles, self.record_bytes // 16, 64, 16), dtype=self._torch().uint8, device=self._dev())
 
@@ -185,7 +197,7 @@ class SkyjoVecEnv:
 
     def reset(self, mask=None, out=None):
         torch = self._torch()
-        out = self._new_step_records() if out is None else out
+        out = self._step_records(out)
         mp = None
         if mask is not None:
             mask = mask.to(device=self._dev(), dtype=torch.uint8).contiguous()
@@ -194,11 +206,13 @@ class SkyjoVecEnv:
         return out
 
     def step(self, actions, out=None):
-        """SimpleSkyjoEnv.step for every game (skyjo_env.py:216-252); actions: int32 cuda tensor [num_envs]."""
+        """SimpleSkyjoEnv.step for every game (skyjo_env.py:216-252); actions: int32 cuda tensor [num_envs].  ``out`` (here and in
+        ``reset`` / ``observe``): one iteration's records in the engine's layout - ``new_records()``, or ``new_planar_records()`` with
+        'tile-planar-all' - or ``ValueError``."""
         torch = self._torch()
         assert actions.is_cuda and actions.dtype == torch.int32 and actions.is_contiguous()
         assert actions.numel() == self.num_envs
-        out = self._new_step_records() if out is None else out
+        out = self._step_records(out)
         _lib.check(self._L.skyjo_vec_step(self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(out.data_ptr()),
                                           self._stream()))
         return out
@@ -219,7 +233,7 @@ class SkyjoVecEnv:
         _lib.check(self._L.skyjo_vec_rollout(self._h, int(iters), int(policy_seed), rp, ap, self._stream()))
 
     def observe(self, players=None, out=None):
-        out = self._new_step_records() if out is None else out
+        out = self._step_records(out)
         pp = C.c_void_p(players.data_ptr()) if players is not None else None
         _lib.check(self._L.skyjo_vec_observe(self._h, pp, C.c_void_p(out.data_ptr()), self._stream()))
         return out

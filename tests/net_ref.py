@@ -70,6 +70,20 @@ def weights(shape, wset):
     return tuple(p)
 
 
+def steered(kind):
+    """Set A (31 -> 26) with a last layer that steers the pair draw: "ties" - every logit 1.25; "ramp" - the logits 0 .. -120 descending
+    in k, whatever the observation; "sharp" - w3 x 60, logits far apart.  A list of six float32 arrays."""
+    p = [np.array(t) for t in weights((31, 26), "A")]
+    if kind == "ties":
+        p[4], p[5] = np.zeros_like(p[4]), np.full_like(p[5], 1.25)
+    elif kind == "ramp":
+        p[4], p[5] = np.zeros_like(p[4]), np.linspace(0.0, -120.0, 26).astype(np.float32)
+    else:
+        assert kind == "sharp"
+        p[4] = (p[4] * np.float32(60.0)).astype(np.float32)
+    return p
+
+
 # ---------------------------------------------------------------- forward references
 def exact(params, x):
     """X: float64 [n, out_dim]."""

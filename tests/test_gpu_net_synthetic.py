@@ -237,24 +237,12 @@ def test_one_lane_draw_on_mask_and_logit_families(no_masking, env64, env_high):
 
 
 # ---------------------------------------------------------------- the pair draw
-def _steered(kind):
-    p = [np.array(t) for t in ref.weights((31, 26), "A")]
-    if kind == "ties":
-        p[4], p[5] = np.zeros_like(p[4]), np.full_like(p[5], 1.25)
-    elif kind == "ramp":
-        p[4], p[5] = np.zeros_like(p[4]), np.linspace(0.0, -120.0, 26).astype(np.float32)
-    else:
-        assert kind == "sharp"
-        p[4] = (p[4] * np.float32(60.0)).astype(np.float32)
-    return p
-
-
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 @pytest.mark.parametrize("kind", ["ties", "ramp", "sharp"])
 def test_pair_draw_equals_one_lane_draw_and_the_reference(kind, precision, env_high):
     import torch
 
-    net = _net(_steered(kind), precision, key=("steered", kind))
+    net = _net(ref.steered(kind), precision, key=("steered", kind))
     seed, ticket = SEED_TICKET[2]
     for no_masking in (False, True):
         case = ref.draw_case(DRAW_ROWS, seed, ticket + no_masking, game_id0=HIGH_ID0, no_masking=no_masking, rng_seed=1)
