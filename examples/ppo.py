@@ -37,10 +37,10 @@ def compute_returns(buf):
     return returns, mask
 
 
-def _ppo_update_native(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae):
+def _ppo_update_native(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, seats=None):
     """``ppo_update(..., native_batches=True)``: the same epochs on minibatches the package builds on the buffer as it lies."""
     compute_targets(buf, gamma=gae[0], lam=gae[1])
-    sel = select_rows(buf, TGT_HAS_TARGET)
+    sel = select_rows(buf, TGT_HAS_TARGET, seats=seats)
     norm = (sel.mean, max(sel.std, 1e-6))
     gen = torch.Generator(device=buf.actions.device).manual_seed(seed)
     stats = []
@@ -66,12 +66,12 @@ def _ppo_update_native(model, buf, optimizer, epochs, minibatch, clip, vf_coef, 
     return {"first": stats[0], "last": stats[-1], "transitions": sel.count}
 
 
-def _ppo_update_native_loss(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip):
+def _ppo_update_native_loss(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip, seats=None):
     """``ppo_update(..., native_batches=True, native_loss=True)``: the minibatches AND the loss head in native calls
     (``learner.ppo_loss``: loss, statistics and the gradients with respect to the model's two outputs in one kernel); autograd runs
     through the two branches only, and the statistics stay on the device until the epoch is over - one read per epoch."""
     compute_targets(buf, gamma=gae[0], lam=gae[1])
-    sel = select_rows(buf, TGT_HAS_TARGET)
+    sel = select_rows(buf, TGT_HAS_TARGET, seats=seats)
     norm = (sel.mean, max(sel.std, 1e-6))
     gen = torch.Generator(device=buf.actions.device).manual_seed(seed)
     out = PPOLossBuffers(max(min(minibatch, sel.count), 1), buf.actions.device)
@@ -94,12 +94,12 @@ def _ppo_update_native_loss(model, buf, optimizer, epochs, minibatch, clip, vf_c
     return {"first": stats[0], "last": stats[-1], "transitions": sel.count}
 
 
-def _ppo_update_native_nets(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip):
+def _ppo_update_native_nets(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip, seats=None):
     """``ppo_update(..., native_batches=True, native_loss=True, native_nets=True)``: the two branches as well - per minibatch gather,
     two forwards, the loss head, two backwards and the optimizer's step, every one a native call (``learner.NativeBranch``): no autograd
     graph, no allocation inside the loop, no ``zero_grad`` (``backward`` overwrites the gradients)."""
     compute_targets(buf, gamma=gae[0], lam=gae[1])
-    sel = select_rows(buf, TGT_HAS_TARGET)
+    sel = select_rows(buf, TGT_HAS_TARGET, seats=seats)
     norm = (sel.mean, max(sel.std, 1e-6))
     gen = torch.Generator(device=buf.actions.device).manual_seed(seed)
     rows = max(min(minibatch, sel.count), 1)
@@ -125,7 +125,7 @@ def _ppo_update_native_nets(model, buf, optimizer, epochs, minibatch, clip, vf_c
 
 
 def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_coef=1.0, seed=0, gae=None, native_batches=False,
-               native_loss=False, ent_coef=0.0, vf_clip=None, native_nets=False):
+               native_loss=False, ent_coef=0.0, vf_clip=None, native_nets=False, seats=None):
     """Clipped-surrogate PPO epochs over the buffer (RLlib defaults: clip_param 0.3, vf_loss_coeff 1.0).  Returns the mean
     losses of the first and the last epoch.  ``gae``: None - Monte-Carlo returns of the episodes that ended inside the buffer
     (``compute_returns``); (gamma, lambda) - advantages, value targets and the row mask of ``rollout.compute_targets`` (one
@@ -135,7 +135,12 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
     ``native_batches``): the loss head is ``learner.ppo_loss`` - one kernel between the model's outputs and ``optimizer.step()``; only
     this path knows ``ent_coef`` (an entropy bonus) and ``vf_clip`` (RLlib's ``vf_clip_param``), and its statistics gain ``entropy``
     and ``clip_fraction``.  ``native_nets`` (needs ``native_loss``): the two branches' forwards and backwards are
-    ``learner.NativeBranch``'s kernels on the float32 parameters - a minibatch step is then a fixed sequence of native launches."""
+    ``learner.NativeBranch``'s kernels on the float32 parameters - a minibatch step is then a fixed sequence of native launches.
+    ``seats`` (needs ``native_batches``): an iterable of seat numbers - the update runs on the rows in which these seats acted, their
+    advantages normalised with their own moments (``rollout.select_rows(buf, seats=...)``): ``model`` is the policy of those seats
+    in a buffer that ``arena.collect`` filled.  None: every row, as before."""
+    if seats is not None and not native_batches:
+        raise ValueError("seats belongs to native_batches=True")
     if native_nets and not native_loss:
         raise ValueError("native_nets=True needs native_loss=True")
     if native_loss:
@@ -144,14 +149,14 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
         if gae is None:
             raise ValueError("native_batches=True needs gae=(gamma, lambda)")
         if native_nets:
-            return _ppo_update_native_nets(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip)
-        return _ppo_update_native_loss(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip)
+            return _ppo_update_native_nets(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip, seats=seats)
+        return _ppo_update_native_loss(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip, seats=seats)
     if ent_coef != 0.0 or vf_clip is not None:
         raise ValueError("ent_coef and vf_clip belong to native_loss=True")
     if native_batches:
         if gae is None:
             raise ValueError("native_batches=True needs gae=(gamma, lambda)")
-        return _ppo_update_native(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae)
+        return _ppo_update_native(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, seats=seats)
     v = buf.views()
     T = buf.T
     if gae is None:
@@ -194,6 +199,28 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
             tot["n"] += n
         stats.append({k: tot[k] / max(tot["n"], 1) for k in ("policy_loss", "vf_loss", "kl")})
     return {"first": stats[0], "last": stats[-1], "transitions": int(idx.numel())}
+
+
+def ppo_update_per_seat(models, buf, optimizers, gae=(0.99, 1.0), native_loss=True, native_nets=False, **kw):
+    """One PPO update per seat that has a model, on a buffer ``arena.collect`` filled with every seat playing its own policy - the
+    reference's set-up, ``policies = {name: ... for name in env.agents}`` with ``policy_mapping_fn = lambda agent_id: agent_id``
+    (``rlskyjo/models/train_model_simple_rllib.py:43-49``).  ``models`` / ``optimizers``: ``buf.N`` entries each, seat s's
+    ``ActionMaskModel`` and its optimizer (a ``learner.NativeAdam`` re-packs the seat's ``FusedNet``s in its ``step``), or None for a
+    seat that does not learn (a frozen or a random opponent).  Seat s runs ``ppo_update(models[s], buf, optimizers[s], seats=(s,),
+    native_batches=True, ...)``: its own rows, normalised with its own moments, as RLlib normalises per policy batch.  Seats that
+    share a model must be updated together: call ``ppo_update(..., seats=(s0, s1))`` yourself.  Returns the list of ``ppo_update``'s
+    results, None for a seat without a model.  ``kw``: ``ppo_update``'s other keywords."""
+    models, optimizers = list(models), list(optimizers)
+    if len(models) != buf.N or len(optimizers) != buf.N:
+        raise ValueError(f"models and optimizers need {buf.N} entries each (None for a seat that does not learn)")
+    if any((m is None) != (o is None) for m, o in zip(models, optimizers)):
+        raise ValueError("a seat has a model and an optimizer, or neither")
+    learners = [m for m in models if m is not None]
+    if len({id(m) for m in learners}) != len(learners):
+        raise ValueError("two seats share a model: update them in one ppo_update(..., seats=(...)) call")
+    return [None if m is None else ppo_update(m, buf, o, gae=gae, native_batches=True, native_loss=native_loss, native_nets=native_nets,
+                                              seats=(s,), **kw)
+            for s, (m, o) in enumerate(zip(models, optimizers))]
 
 
 def repack(model, device=0):

@@ -493,6 +493,22 @@ int skyjo_vec_rollout_select(skyjo_vec *h, const uint8_t *flags, int64_t n_rows,
                              const float *advantages /* may be NULL */, int64_t *index_out /* [n_rows] */,
                              int64_t *count_out /* device, 1 */, double *moments_out /* device, 2; NULL iff advantages is NULL */,
                              void *stream);
+/* skyjo_vec_rollout_select_seats: skyjo_vec_rollout_select over the n_rows = T * num_envs rows of a buffer, restricted to the rows in which
+ * one of a set of seats acted - a row needs  (flags[r] & require_bits) == require_bits  AND bit agent(r) of seat_mask, agent(r) the agent
+ * byte of the row's record, read in place from records[0 .. T) in `layout` (row r is game r % num_envs of step r / num_envs; the
+ * padding slots of a tile-planar buffer are no rows).  The per-seat minibatches of a buffer in which every seat trains a policy of its
+ * own (skyjo_vec_arena_collect): the moments are those of the chosen seats' rows alone.  The same three launches, the same reduction
+ * shape, no atomics, the handle's scratch: the same input gives the same bits on every call, and with every seat in seat_mask index,
+ * count and moments carry the bits of skyjo_vec_rollout_select.
+ *   records    as for skyjo_vec_rollout_targets; only the agent byte is read;  T >= 1
+ *   seat_mask  bit s = seat s takes part; non-zero, no bit at or above num_players
+ *   flags, require_bits, advantages, index_out, count_out, moments_out: as for skyjo_vec_rollout_select
+ * SKYJO_E_INVALID (nothing is launched): a null pointer, T < 1, require_bits outside 1 .. 255, a seat_mask of 0 or with a bit at or above
+ * num_players, advantages without moments_out or the reverse, a layout that is neither SKYJO_REC_ROW_MAJOR nor SKYJO_REC_TILE_PLANAR. */
+int skyjo_vec_rollout_select_seats(skyjo_vec *h, const void *records, int32_t layout, int32_t T, const uint8_t *flags,
+                                   int32_t require_bits, uint32_t seat_mask, const float *advantages /* may be NULL */,
+                                   int64_t *index_out /* [T * num_envs] */, int64_t *count_out /* device, 1 */,
+                                   double *moments_out /* device, 2; NULL iff advantages is NULL */, void *stream);
 /* skyjo_vec_rollout_gather: the rows index[0 .. m) of the buffer - row ids r = t * num_envs + b, 0 <= r < T * num_envs, in any order,
  * repeats allowed (a learner passes a shuffled slice of the selection) - as dense [m]-major outputs, one kernel:
  *   records        the buffer's records in `layout` (as for skyjo_vec_rollout_targets; row r is record b of step t), 16-byte aligned
@@ -621,6 +637,44 @@ int skyjo_vec_arena_select(skyjo_vec *h, const skyjo_vec_seat_policy *seats /* [
 int skyjo_vec_arena_rollout(skyjo_vec *h, const skyjo_vec_seat_policy *seats /* [num_players] */, int32_t T, uint64_t seed,
                             uint64_t first_ticket, const skyjo_vec_rollout_buffers *buffers /* logp and values must be NULL */,
                             void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Arena rollouts a learner can train on: one policy PER SEAT, as the reference's script trains them (train_model_simple_rllib.py:43-49:
+ * a PPO policy per agent, policy_mapping_fn = agent id).  The iteration of skyjo_vec_arena_select, which also records, per game, the
+ * log-probability of the chosen action and the value estimate of the ACTING seat's own value net - the two columns
+ * skyjo_vec_rollout_targets, _select_seats, _gather and skyjo_vec_ppo_loss need to train seat s on the rows in which seat s acted.
+ *   seats       as for skyjo_vec_arena_select
+ *   value_nets  num_players entries, value_nets[s] = the value net of seat s or NULL; a net needs out_dim 1, the engine's observation
+ *               and the engine's device.  Seats that share a pointer share one forward.
+ * skyjo_vec_arena_act, one lockstep iteration: one full-batch launch of the net kernel per distinct policy net and one per distinct value
+ * net into their slices of the workspace, then ONE kernel, one lane per game:
+ *   actions_out[g]  exactly skyjo_vec_arena_select's action for the same (seats, records, seed, ticket)
+ *   logp_out[g]     (m[a] - mx) - log(sum): a = the action, m = the masked logits, mx their maximum, sum the float32 sum of
+ *                   exp(m - mx) in the draw's order (blocks of four actions, block totals left to right).  SKYJO_SEAT_SAMPLE: the bits
+ *                   skyjo_vec_sample_actions and skyjo_vec_mlp_act write;  SKYJO_SEAT_GREEDY: the same expression at the argmax;
+ *                   SKYJO_SEAT_RANDOM: the same expression on 26 zero logits, - log(number of legal actions)
+ *   values_out[g]   output 0 of value_nets[seat] on record g - the bits skyjo_vec_mlp_forward_layout gives - or 0.0f where it is NULL
+ * actions_out and logp_out are both set or both NULL.  Both NULL: values_out only, no policy net is launched - the bootstrap row of a
+ * buffer, selected by the seat the record expects.  Launches per iteration: distinct policy nets + distinct value nets + 1 (+ the step).
+ *   workspace   device memory of the caller, 16-byte aligned, at least skyjo_vec_arena_act_workspace_bytes(h, distinct policy nets,
+ *               distinct value nets) bytes: the policy slices of skyjo_vec_arena_select first, then per distinct value net float32
+ *               [num_envs], rounded up to a multiple of 16 bytes.  With no net at all it may be NULL / 0.
+ * skyjo_vec_arena_collect: T iterations of  [the forwards] -> [that kernel] -> [skyjo_vec_step_collect], then the values-only pass on
+ * records[T], on one stream, nothing read back.  buffers as for skyjo_vec_model_rollout, in the layout the engine's step writes
+ * (SKYJO_OPT_RECORD_LAYOUT), EVERY column required; values is float32 [T+1][num_envs][1].  Iteration t draws with ticket
+ * first_ticket + t: with every seat SKYJO_SEAT_SAMPLE on one policy net and every seat on one value net, all six columns carry the bits of
+ * skyjo_vec_model_rollout.
+ * SKYJO_E_INVALID (nothing is launched): what skyjo_vec_arena_select / _rollout refuse, and a null value_nets, values_out or column, only
+ * one of actions_out / logp_out, a value net whose out_dim is not 1, whose obs_dim is not the engine's or that lives on another device. */
+int64_t skyjo_vec_arena_act_workspace_bytes(const skyjo_vec *h, int32_t distinct_policy_nets,
+                                            int32_t distinct_value_nets); /* 0 for NULL or a count outside 0 .. 12 */
+int skyjo_vec_arena_act(skyjo_vec *h, const skyjo_vec_seat_policy *seats /* [num_players] */,
+                        const skyjo_vec_mlp *const *value_nets /* [num_players], entries may be NULL */, const void *records, int32_t layout,
+                        uint64_t seed, uint64_t ticket, int32_t *actions_out /* [num_envs] or NULL */, float *logp_out /* NULL iff actions_out is */,
+                        float *values_out /* [num_envs] */, void *workspace, int64_t workspace_bytes, void *stream);
+int skyjo_vec_arena_collect(skyjo_vec *h, const skyjo_vec_seat_policy *seats /* [num_players] */,
+                            const skyjo_vec_mlp *const *value_nets /* [num_players], entries may be NULL */, int32_t T, uint64_t seed,
+                            uint64_t first_ticket, const skyjo_vec_rollout_buffers *buffers /* every column required */, void *workspace,
+                            int64_t workspace_bytes, void *stream);
 
 /* Per-seat results of the episodes that ended inside a buffer: over the rows = T * num_envs rows of its final_rewards (double
  * [rows][num_players]) and episode_end (uint8 [rows]) columns, one kernel plus a single-workgroup reduction, all in double, in a fixed

@@ -130,6 +130,10 @@ SIGNATURES = {
     "skyjo_vec_arena_workspace_bytes": (I64, [VP, I32]),
     "skyjo_vec_arena_select": (C.c_int, [VP, C.POINTER(SeatPolicy), VP, I32, U64, U64, VP, VP, I64, VP]),
     "skyjo_vec_arena_rollout": (C.c_int, [VP, C.POINTER(SeatPolicy), I32, U64, U64, C.POINTER(RolloutBuffers), VP, I64, VP]),
+    "skyjo_vec_arena_act_workspace_bytes": (I64, [VP, I32, I32]),
+    "skyjo_vec_arena_act": (C.c_int, [VP, C.POINTER(SeatPolicy), C.POINTER(VP), VP, I32, U64, U64, VP, VP, VP, VP, I64, VP]),
+    "skyjo_vec_arena_collect": (C.c_int, [VP, C.POINTER(SeatPolicy), C.POINTER(VP), I32, U64, U64, C.POINTER(RolloutBuffers), VP, I64, VP]),
+    "skyjo_vec_rollout_select_seats": (C.c_int, [VP, VP, I32, I32, VP, I32, U32, VP, VP, VP, VP, VP]),
     "skyjo_vec_episode_stats_scratch_bytes": (I64, [I64, I32]),
     "skyjo_vec_episode_stats": (C.c_int, [VP, VP, I64, I32, VP, VP, I64, VP]),
     "skyjo_vec_rewards_ptr": (VP, [VP]),

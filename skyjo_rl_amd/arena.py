@@ -13,6 +13,11 @@ logits, the smallest index on a tie - or ``"random"`` - ``policy_ra``, uniform o
 model's policy branch; seats that hold the same ``FusedNet`` share its forward.  ``episode_stats`` turns the ``final_rewards`` /
 ``episode_end`` columns of a played buffer into episodes, mean and standard deviation of the final reward and win rate per seat
 (``skyjo_vec_episode_stats``).
+
+``collect`` (``act`` for one iteration) is the arena rollout a learner can train on - the reference's own set-up, one PPO policy per
+seat: it also records ``logp`` and the ACTING seat's own value estimate (``skyjo_vec_arena_collect``: per iteration one launch per
+distinct policy net, one per distinct value net, one kernel, the step), so that ``rollout.compute_targets`` and the per-seat
+``rollout.select_rows(buf, seats=...)`` / ``minibatches(..., seats=...)`` apply to the buffer.
 """
 import ctypes as C
 import math
@@ -117,6 +122,110 @@ def play(env, seats, buf, seed=0, first_ticket=0, first_records=None):
     vp = lambda t: t.data_ptr()
     b = _lib.RolloutBuffers(vp(buf.records), vp(buf.actions), None, None, vp(buf.final_rewards), vp(buf.episode_end))
     _lib.check(_lib.load().skyjo_vec_arena_rollout(env._h, sp, buf.T, int(seed), int(first_ticket), C.byref(b), ws, nbytes, env._stream()))
+    return buf
+
+
+def value_nets(env, values):
+    """The ctypes array ``const skyjo_vec_mlp *[num_players]`` for ``values``: a list of ``env.num_players`` entries, each the
+    ``FusedNet`` of a model's value branch or None.  The array keeps its nets alive (``.nets``).  ``ValueError`` for a wrong length, an
+    entry that is neither, or a closed net."""
+    values = list(values)
+    if len(values) != env.num_players:
+        raise ValueError(f"values has {len(values)} entries, the engine has {env.num_players} players")
+    arr = (C.c_void_p * len(values))()
+    nets = []
+    for s, net in enumerate(values):
+        if net is None:
+            continue
+        if not hasattr(net, "_h"):
+            raise ValueError(f"seat {s}: a value net is a FusedNet or None, not {net!r}")
+        handle = net._h
+        if not handle:
+            raise ValueError(f"seat {s}: this FusedNet is closed")
+        if not any(n is net for n in nets):
+            nets.append(net)
+        arr[s] = handle.value if isinstance(handle, C.c_void_p) else handle
+    arr.nets = nets
+    return arr
+
+
+def _values(env, values):
+    return values if isinstance(values, C.Array) and getattr(values, "_type_", None) is C.c_void_p else value_nets(env, values)
+
+
+def _act_workspace(env, holder, sp, vn):
+    """(pointer, bytes) of a workspace for the distinct policy nets of ``sp`` and the distinct value nets of ``vn``, cached on ``holder``
+    (where ``play`` caches its own: the larger of the two serves both); (None, 0) when no seat has a net of either kind."""
+    need = int(_lib.load().skyjo_vec_arena_act_workspace_bytes(env._h, len({s.net for s in sp if s.net}), len({v for v in vn if v})))
+    if need == 0:
+        return None, 0
+    ws = getattr(holder, "_arena_workspace", None)
+    if ws is None or ws.numel() < need:
+        torch = env._torch()
+        ws = torch.empty((need,), dtype=torch.uint8, device=env._dev())
+        holder._arena_workspace = ws
+    return C.c_void_p(ws.data_ptr()), ws.numel()
+
+
+def act(env, seats, values, records, seed=0, ticket=0, actions=None, logp=None, values_out=None, planar=False, workspace=None,
+        values_only=False):
+    """One lockstep iteration with the learner's columns (``skyjo_vec_arena_act``): ``(actions, logp, values_out)`` - ``select``'s
+    actions (the same bits), float32 [num_envs] the log-probability of each under the acting seat's masked distribution, and float32
+    [num_envs] the acting seat's own value estimate (0.0 for a seat without a value net).  ``seats`` / ``records`` / ``planar`` /
+    ``workspace``: as for ``select``; ``values``: ``num_players`` entries, each a ``FusedNet`` of a value branch or None (or the
+    result of ``value_nets``).  ``values_only``: no action is chosen and no policy net runs - ``(None, None, values_out)``, the
+    bootstrap values of the records a rollout ends on."""
+    torch = env._torch()
+    sp, vn = _seats(env, seats), _values(env, values)
+    want = (env.tiles * 64 if planar else env.num_envs) * env.record_bytes
+    if not records.is_contiguous() or records.numel() != want or records.dtype != torch.uint8:
+        raise ValueError(f"records must be one iteration's contiguous uint8 records ({want} bytes with planar={planar})")
+
+    def column(name, t, dtype):
+        if t is None:
+            return torch.empty((env.num_envs,), dtype=dtype, device=env._dev())
+        if t.dtype != dtype or t.numel() != env.num_envs or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} tensor of num_envs elements")
+        return t
+
+    if values_only:
+        if actions is not None or logp is not None:
+            raise ValueError("values_only=True takes neither actions nor logp")
+    else:
+        actions, logp = column("actions", actions, torch.int32), column("logp", logp, torch.float32)
+    values_out = column("values_out", values_out, torch.float32)
+    ws, nbytes = _act_workspace(env, sp if workspace is None else workspace, sp, vn)
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _lib.check(_lib.load().skyjo_vec_arena_act(env._h, sp, vn, vp(records), _lib.REC_TILE_PLANAR if planar else _lib.REC_ROW_MAJOR, int(seed),
+                                               int(ticket), vp(actions), vp(logp), vp(values_out), ws, nbytes, env._stream()))
+    return actions, logp, values_out
+
+
+def collect(env, seats, values, buf, seed=0, first_ticket=0, first_records=None):
+    """Fill ALL SIX columns of ``buf`` (a ``rollout.RolloutBuffer`` of ``env``) with T lockstep iterations of the seats' policies in one
+    native call (``skyjo_vec_arena_collect``): what ``play`` writes, and ``logp`` - the log-probability of the chosen action under the
+    acting seat's masked distribution, for a sampled, a greedy and a random seat alike - and ``values`` [T + 1, B, 1] - the value net of
+    the seat that acts in the row, ``values[T]`` that of the seat ``records[T]`` expects, 0.0 for a seat without one.  The buffer then
+    goes through ``rollout.compute_targets`` unchanged, and ``rollout.select_rows(buf, seats=(s,))`` / ``minibatches(..., seats=(s,))``
+    give seat s its own rows: one learner per seat at one table, a seat against frozen versions of itself, a seat against ``"random"``
+    seats.  ``seats``: as for ``play``; ``values``: ``num_players`` entries, each a ``FusedNet`` of a value branch or None.  With every
+    seat ``("sample", P)`` and every value ``V`` these are the bits of ``rollout.collect(env, P, V, buf)``.  The workspace is cached on
+    the buffer."""
+    from . import rollout
+
+    rollout._check_records(buf)
+    if buf.planar != (env.record_layout == "tile-planar-all"):
+        raise ValueError(f"buf.planar={buf.planar}, but the engine's record layout is {env.record_layout!r}")
+    if buf.B != env.num_envs or buf.N != env.num_players:
+        raise ValueError("buf was made for another engine shape")
+    if tuple(buf.values.shape) != (buf.T + 1, buf.B, 1):
+        raise ValueError(f"buf.values must be [T + 1, B, 1], not {tuple(buf.values.shape)}")
+    sp, vn = _seats(env, seats), _values(env, values)
+    ws, nbytes = _act_workspace(env, buf, sp, vn)
+    rollout._first(env, buf, first_records)
+    vp = lambda t: t.data_ptr()
+    b = _lib.RolloutBuffers(vp(buf.records), vp(buf.actions), vp(buf.logp), vp(buf.values), vp(buf.final_rewards), vp(buf.episode_end))
+    _lib.check(_lib.load().skyjo_vec_arena_collect(env._h, sp, vn, buf.T, int(seed), int(first_ticket), C.byref(b), ws, nbytes, env._stream()))
     return buf
 
 

@@ -93,6 +93,77 @@ __global__ __launch_bounds__(SK_SEL_THREADS) void k_select_pass(const uint8_t *f
   }
 }
 
+// k_select_pass restricted to a set of seats (skyjo_vec_rollout_select_seats): a row also needs bit agent(row) of seat_mask, the agent
+// byte read in place from the row's record - row r is game r % B of step r / B, record (r / B) * rec_stride + r % B (rec_stride: B
+// row-major, tiles * 64 tile-planar: k_gather_rows' numbers, so the padding slots of a partial tile are never rows).  The walk, the
+// ballots, the shape of the sums and the two outputs are k_select_pass's, statement for statement: with every seat in the mask the
+// counts, the offsets and the sums carry the same bits, and k_select_scan serves both.
+struct SkSelectSeats {
+  const uint8_t *rec;
+  long long rec_stride;
+  uint32_t seat_mask;
+  int32_t B, rec_bytes, off_agent, planar;
+};
+
+template <bool SCATTER>
+__global__ __launch_bounds__(SK_SEL_THREADS) void k_select_pass_seats(const uint8_t *flags, long long n, uint32_t require, const float *adv,
+                                                                     long long *block_count, double *block_sum, long long *index_out,
+                                                                     SkSelectSeats st) {
+  __shared__ uint32_t wcnt[SK_SEL_WAVES];
+  __shared__ double wsum[SK_SEL_WAVES], wsq[SK_SEL_WAVES];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long r0 = (long long)blockIdx.x * SK_SEL_ROWS + w * SK_SEL_WAVE_ROWS + lane;
+  uint32_t f[SK_SEL_ITERS], seat[SK_SEL_ITERS];
+  float av[SK_SEL_ITERS];
+#pragma unroll
+  for (int k = 0; k < SK_SEL_ITERS; k++) {
+    const long long r = r0 + k * 64;
+    f[k] = r < n ? flags[r] : 0u;  // (require is never 0: a row past the end is not selected)
+    seat[k] = 0u;
+    if (r < n) {
+      const long long t = r / st.B, q = st.planar ? t * st.rec_stride + (r - t * st.B) : r;
+      seat[k] = *sk_rec_byte(st.rec, q, st.off_agent, st.rec_bytes, st.planar);
+    }
+    av[k] = 0.f;
+    if (!SCATTER && adv && r < n) av[k] = adv[r];
+  }
+  unsigned long long bal[SK_SEL_ITERS];
+  uint32_t cnt = 0;
+  double s = 0.0, q = 0.0;
+#pragma unroll
+  for (int k = 0; k < SK_SEL_ITERS; k++) {
+    const bool sel = (f[k] & require) == require && seat[k] < 32u && ((st.seat_mask >> seat[k]) & 1u) != 0u;
+    bal[k] = __ballot(sel);
+    cnt += (uint32_t)__popcll(bal[k]);
+    if (!SCATTER) {
+      const double a = sel ? (double)av[k] : 0.0;
+      s += a;
+      q += a * a;
+    }
+  }
+  if (!SCATTER && adv) s = sk_wave_sum(s), q = sk_wave_sum(q);
+  if (lane == 0) wcnt[w] = cnt, wsum[w] = s, wsq[w] = q;
+  __syncthreads();
+  if constexpr (!SCATTER) {
+    if (threadIdx.x == 0) {
+      block_count[blockIdx.x] = (long long)((wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]));
+      if (adv) {
+        block_sum[2 * (size_t)blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+        block_sum[2 * (size_t)blockIdx.x + 1] = ((wsq[0] + wsq[1]) + wsq[2]) + wsq[3];
+      }
+    }
+  } else {
+    long long off = block_count[blockIdx.x];
+    for (int i = 0; i < w; i++) off += wcnt[i];
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int k = 0; k < SK_SEL_ITERS; k++) {
+      if ((bal[k] >> lane) & 1ull) index_out[off + __popcll(bal[k] & below)] = r0 + k * 64;
+      off += __popcll(bal[k]);
+    }
+  }
+}
+
 // Phase 2, one workgroup: block_count[0 .. nb) becomes its exclusive scan; the total, and the two sums over the blocks' partials
 // (thread t owns a contiguous span of blocks, then the wavefront's tree, then the wavefronts in order), go to count_out /
 // moments_out.  nb == 0 writes the zeros.

@@ -269,6 +269,43 @@ int skyjo_vec_rollout_select(skyjo_vec *h, const uint8_t *flags, int64_t n_rows,
   return SKYJO_OK;
 }
 
+int skyjo_vec_rollout_select_seats(skyjo_vec *h, const void *records, int32_t layout, int32_t T, const uint8_t *flags, int32_t require_bits,
+                                   uint32_t seat_mask, const float *advantages, int64_t *index_out, int64_t *count_out, double *moments_out,
+                                   void *stream) {
+  static const char *who = "skyjo_vec_rollout_select_seats";
+  if (!h || !records || !flags || !index_out || !count_out) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
+  if ((advantages == nullptr) != (moments_out == nullptr)) return fail(SKYJO_E_INVALID, std::string(who) + ": advantages and moments_out go together");
+  if (T < 1) return fail(SKYJO_E_INVALID, std::string(who) + ": T must be at least 1");
+  if (require_bits < 1 || require_bits > 255) return fail(SKYJO_E_INVALID, std::string(who) + ": require_bits must lie in 1 .. 255");
+  if (int rc = check_layout(layout)) return rc;
+  const SkEngineView e = sk_engine_view(h);
+  const SkLayout &L = *e.L;
+  if (seat_mask == 0u || (seat_mask >> L.N) != 0u) return fail(SKYJO_E_INVALID, std::string(who) + ": seat_mask must be non-zero and name seats below num_players only");
+  const int64_t n_rows = (int64_t)T * e.B;
+  if (n_rows > (int64_t)SK_SEL_ROWS * 0x7fffffff) return fail(SKYJO_E_INVALID, std::string(who) + ": T * num_envs out of range");
+  DevGuard guard_(e.device_id);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t nb = (size_t)((n_rows + SK_SEL_ROWS - 1) / SK_SEL_ROWS);
+  void *scratch = nullptr;
+  size_t cap = 0;
+  if (int rc = sk_engine_select_scratch(h, nb, &scratch, &cap)) return rc;
+  long long *counts = (long long *)scratch;
+  double *sums = (double *)(counts + cap);
+  SkSelectSeats st{};
+  st.rec = (const uint8_t *)records, st.planar = layout == SKYJO_REC_TILE_PLANAR;
+  st.rec_stride = st.planar ? (long long)e.G : (long long)e.B;
+  st.seat_mask = seat_mask, st.B = e.B, st.rec_bytes = L.rec_bytes, st.off_agent = L.Dp + 26;
+  hipLaunchKernelGGL(k_select_pass_seats<false>, dim3((unsigned)nb), dim3(SK_SEL_THREADS), 0, s, flags, (long long)n_rows, (uint32_t)require_bits,
+                     advantages, counts, sums, (long long *)nullptr, st);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(SK_SCAN_THREADS), 0, s, counts, (const double *)sums, (int)nb, (long long *)count_out, moments_out);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_select_pass_seats<true>, dim3((unsigned)nb), dim3(SK_SEL_THREADS), 0, s, flags, (long long)n_rows, (uint32_t)require_bits,
+                     (const float *)nullptr, counts, sums, (long long *)index_out, st);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
 int skyjo_vec_rollout_gather(skyjo_vec *h, const void *records, int32_t layout, int32_t T, const int64_t *index, int64_t m,
                              const int32_t *actions, const float *logp, const float *values, int32_t value_stride, const float *advantages,
                              const float *value_targets, float adv_mean, float adv_std, float *obs_out, float *logmask_out,
@@ -480,6 +517,70 @@ int arena_launch(const ArenaPlan &p, const uint8_t *rec, int planar, uint64_t se
   return SKYJO_OK;
 }
 
+// ---- the arena iteration that records learner columns (skyjo_vec_arena_act / _collect; the kernel: k_arena_act) ----
+struct ArenaActPlan {
+  ArenaPlan p;
+  const skyjo_vec_mlp *vnet[SKYJO_MAX_PLAYERS] = {};  // the distinct value nets, in the order of their first seat
+  int vnets = 0;
+  uint64_t seat_vnet = 0;
+  float *values = nullptr;  // the value slices: behind the policy slices of the workspace
+};
+
+int64_t arena_act_bytes(int32_t B, int nets, int vnets) {
+  return ((int64_t)nets * sk_arena_slice(B) + (int64_t)vnets * sk_arena_vslice(B)) * (int64_t)sizeof(float);
+}
+
+// arena_plan's checks, the value nets and the larger workspace; 0 or the code fail() returned
+int arena_act_plan(const char *who, const skyjo_vec *h, const skyjo_vec_seat_policy *seats, const skyjo_vec_mlp *const *value_nets, void *workspace,
+                   int64_t workspace_bytes, ArenaActPlan &q) {
+  const std::string name(who);
+  if (!h || !seats || !value_nets) return fail(SKYJO_E_INVALID, name + ": null argument");
+  if (int rc = arena_plan(who, h, seats, workspace, workspace_bytes, q.p)) return rc;
+  const SkLayout &L = *q.p.e.L;
+  for (int s = 0; s < L.N; s++) {
+    const skyjo_vec_mlp *m = value_nets[s];
+    int j = (int)SK_ARENA_NO_VNET;
+    if (m) {
+      if (m->net.out_dim != 1) return fail(SKYJO_E_INVALID, name + ": a seat's value net needs 1 output");
+      if (m->device_id != q.p.e.device_id || m->obs_dim != L.D)
+        return fail(SKYJO_E_INVALID, name + ": a seat's value net must live on the engine's device and take the engine's observation");
+      for (j = 0; j < q.vnets && q.vnet[j] != m; j++) {}
+      if (j == q.vnets) q.vnet[q.vnets++] = m;
+    }
+    q.seat_vnet |= (uint64_t)j << (4 * s);
+  }
+  if (q.p.a.nets + q.vnets) {
+    if (!workspace) return fail(SKYJO_E_INVALID, name + ": seats with nets need a workspace");
+    if ((uintptr_t)workspace & 15) return fail(SKYJO_E_INVALID, name + ": workspace must be 16-byte aligned");
+    if (workspace_bytes < arena_act_bytes(q.p.e.B, q.p.a.nets, q.vnets))
+      return fail(SKYJO_E_INVALID, name + ": workspace is smaller than skyjo_vec_arena_act_workspace_bytes");
+    q.values = (float *)workspace + (size_t)q.p.a.nets * sk_arena_slice(q.p.e.B);
+  }
+  return SKYJO_OK;
+}
+
+// one lockstep iteration: a full-batch forward per distinct policy net (none when actions is null) and per distinct value net, then ONE k_arena_act
+int arena_act_launch(const ArenaActPlan &q, const uint8_t *rec, int planar, uint64_t seed, uint64_t ticket, int32_t *actions, float *logp,
+                     float *values_out, hipStream_t s) {
+  SkArenaActArgs aa{};
+  aa.s = q.p.a;
+  SkArenaArgs &a = aa.s;
+  a.rec = rec, a.planar = planar, a.seed = seed, a.ticket = ticket, a.actions = actions;
+  aa.logp = logp, aa.values_out = values_out, aa.values = q.values, aa.seat_vnet = q.seat_vnet;
+  const SkMlpDraw nodraw{};
+  for (int j = 0; actions && j < a.nets; j++)
+    if (int rc = launch_mlp(q.p.net[j], q.p.net[j], 1, rec, (int)a.rec_bytes, q.p.net[j]->obs_dim, (int64_t)a.n,
+                            const_cast<float *>(a.logits) + (size_t)j * sk_arena_slice(a.n), nodraw, nullptr, s, planar))
+      return rc;
+  for (int j = 0; j < q.vnets; j++)
+    if (int rc = launch_mlp(q.vnet[j], q.vnet[j], 1, rec, (int)a.rec_bytes, q.vnet[j]->obs_dim, (int64_t)a.n,
+                            q.values + (size_t)j * sk_arena_vslice(a.n), nodraw, nullptr, s, planar))
+      return rc;
+  hipLaunchKernelGGL(k_arena_act, dim3((unsigned)((a.n + SK_ARENA_BLOCK - 1) / SK_ARENA_BLOCK)), dim3(SK_ARENA_BLOCK), 0, s, aa);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
 constexpr int64_t kStatMaxRows = (int64_t)SK_STAT_ROWS << 30;
 
 }  // namespace
@@ -521,6 +622,55 @@ int skyjo_vec_arena_rollout(skyjo_vec *h, const skyjo_vec_seat_policy *seats, in
     }
     if (int rc = skyjo_vec_step_collect(h, act, rec + (size_t)(t + 1) * per_it, b->final_rewards + (size_t)t * B * N, b->episode_end + (size_t)t * B, stream))
       return rc;
+  }
+  return SKYJO_OK;
+}
+
+int64_t skyjo_vec_arena_act_workspace_bytes(const skyjo_vec *h, int32_t distinct_policy_nets, int32_t distinct_value_nets) {
+  if (!h || distinct_policy_nets < 0 || distinct_policy_nets > SKYJO_MAX_PLAYERS || distinct_value_nets < 0 || distinct_value_nets > SKYJO_MAX_PLAYERS)
+    return 0;
+  return arena_act_bytes(sk_engine_view(h).B, distinct_policy_nets, distinct_value_nets);
+}
+
+int skyjo_vec_arena_act(skyjo_vec *h, const skyjo_vec_seat_policy *seats, const skyjo_vec_mlp *const *value_nets, const void *records, int32_t layout,
+                        uint64_t seed, uint64_t ticket, int32_t *actions_out, float *logp_out, float *values_out, void *workspace,
+                        int64_t workspace_bytes, void *stream) {
+  static const char *who = "skyjo_vec_arena_act";
+  if (!records || !values_out) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
+  if ((actions_out == nullptr) != (logp_out == nullptr)) return fail(SKYJO_E_INVALID, std::string(who) + ": actions_out and logp_out go together");
+  if (int rc = check_layout(layout)) return rc;
+  ArenaActPlan q;
+  if (int rc = arena_act_plan(who, h, seats, value_nets, workspace, workspace_bytes, q)) return rc;
+  DevGuard guard_(q.p.e.device_id);
+  return arena_act_launch(q, (const uint8_t *)records, (int)(layout == SKYJO_REC_TILE_PLANAR), seed, ticket, actions_out, logp_out, values_out,
+                          (hipStream_t)stream);
+}
+
+int skyjo_vec_arena_collect(skyjo_vec *h, const skyjo_vec_seat_policy *seats, const skyjo_vec_mlp *const *value_nets, int32_t T, uint64_t seed,
+                            uint64_t first_ticket, const skyjo_vec_rollout_buffers *b, void *workspace, int64_t workspace_bytes, void *stream) {
+  static const char *who = "skyjo_vec_arena_collect";
+  if (!b || !b->records || !b->actions || !b->logp || !b->values || !b->final_rewards || !b->episode_end)
+    return fail(SKYJO_E_INVALID, std::string(who) + ": null argument (every column of the buffers is required)");
+  if (T < 1) return fail(SKYJO_E_INVALID, std::string(who) + ": T must be at least 1");
+  ArenaActPlan q;
+  if (int rc = arena_act_plan(who, h, seats, value_nets, workspace, workspace_bytes, q)) return rc;
+  int64_t lay = 0;  // what skyjo_vec_step_collect writes: as skyjo_vec_arena_rollout decides it
+  if (int rc = skyjo_vec_get_option(h, SKYJO_OPT_RECORD_LAYOUT, &lay)) return rc;
+  const int planar = lay == SKYJO_REC_TILE_PLANAR_ALL;
+  const SkEngineView &e = q.p.e;
+  const size_t B = (size_t)e.B, N = (size_t)e.L->N, per_it = (planar ? e.G : B) * (size_t)e.L->rec_bytes;
+  uint8_t *rec = (uint8_t *)b->records;
+  for (int t = 0; t <= T; t++) {  // t == T: the values-only pass on the records the rollout ends on
+    int32_t *act = t < T ? b->actions + (size_t)t * B : nullptr;
+    {
+      DevGuard guard_(e.device_id);
+      if (int rc = arena_act_launch(q, rec + (size_t)t * per_it, planar, seed, first_ticket + (uint64_t)t, act, t < T ? b->logp + (size_t)t * B : nullptr,
+                                    b->values + (size_t)t * B, (hipStream_t)stream))
+        return rc;
+    }
+    if (t < T)
+      if (int rc = skyjo_vec_step_collect(h, act, rec + (size_t)(t + 1) * per_it, b->final_rewards + (size_t)t * B * N, b->episode_end + (size_t)t * B, stream))
+        return rc;
   }
   return SKYJO_OK;
 }

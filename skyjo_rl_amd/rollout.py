@@ -12,6 +12,9 @@ batches - ``advantages`` and ``value_targets`` by GAE per agent trajectory - in 
 carry a target, the moments of their advantages, and shuffled minibatches as dense float tensors - again on the buffer as it lies
 (``skyjo_vec_rollout_select`` / ``_gather``): no row-major copy of a tile-planar buffer, no knowledge of the record layout.
 ``learner.ppo_loss`` takes a ``Minibatch`` and the model's two outputs from there: the PPO loss head and its gradients in one kernel.
+Where every seat trains a policy of its own (``arena.collect`` fills the same buffer with per-seat ``logp`` and ``values``),
+``select_rows`` / ``minibatches`` take ``seats``: the rows in which those seats acted, with the moments of their advantages alone
+(``skyjo_vec_rollout_select_seats``).
 """
 import ctypes as C
 import math
@@ -137,17 +140,32 @@ def _check_records(buf):
         raise ValueError(f"buf.records has shape {tuple(r.shape)}, but planar={buf.planar} means {want}")
 
 
+def _seat_mask(buf, seats):
+    """The bit mask of ``seats`` (an iterable of seat numbers below ``buf.N``, at least one), or ``ValueError``."""
+    mask = 0
+    for s in seats:
+        if isinstance(s, bool) or int(s) != s or not 0 <= int(s) < buf.N:
+            raise ValueError(f"seats holds {s!r}: seat numbers are integers in 0 .. {buf.N - 1}")
+        mask |= 1 << int(s)
+    if not mask:
+        raise ValueError("seats is empty: name at least one seat, or pass None for every seat")
+    return mask
+
+
 @torch.no_grad()
-def select_rows(buf, require=_lib.TGT_HAS_TARGET):
+def select_rows(buf, require=_lib.TGT_HAS_TARGET, seats=None):
     """The rows of a buffer whose ``target_flags`` have every bit of ``require`` (``compute_targets`` must have run), in one native
     call (``skyjo_vec_rollout_select``): ``Selection(index, count, mean, std)`` - ``index`` int64 [count], ascending row ids
     ``t * B + b`` (what ``torch.nonzero`` gives; a view of ``buf.row_index``, int64 [T * B], allocated once and refilled by every
     call), ``mean`` / ``std`` Python floats: the moments of the selected rows' ``advantages``, computed in double from the two sums
     the kernel returns, ``std`` unbiased like ``torch.std`` (0.0 for fewer than two rows).  Reading back the count (with the sums,
-    one copy) is the only synchronisation."""
+    one copy) is the only synchronisation.  ``seats``: an iterable of seat numbers - only the rows in which one of these seats acted
+    (``skyjo_vec_rollout_select_seats``: the record's agent byte, read in place), with the moments of those rows alone: a seat that
+    trains a policy of its own on an ``arena.collect`` buffer; None: every seat."""
     if getattr(buf, "target_flags", None) is None:
         raise ValueError("select_rows needs the columns of compute_targets(buf)")
     _check_records(buf)
+    mask = None if seats is None else _seat_mask(buf, seats)
     L = _lib.load()
     n = buf.T * buf.B
     if getattr(buf, "row_index", None) is None:
@@ -155,8 +173,13 @@ def select_rows(buf, require=_lib.TGT_HAS_TARGET):
         buf.row_index = torch.empty((n,), dtype=torch.int64, device=dev)
         buf._select_out = torch.empty((3,), dtype=torch.int64, device=dev)  # the count, then the two sums (as doubles)
     out = buf._select_out
-    _lib.check(L.skyjo_vec_rollout_select(buf._env._h, buf.target_flags.data_ptr(), n, int(require), buf.advantages.data_ptr(),
-                                          buf.row_index.data_ptr(), out.data_ptr(), out[1:].data_ptr(), buf._env._stream()))
+    if mask is None:
+        _lib.check(L.skyjo_vec_rollout_select(buf._env._h, buf.target_flags.data_ptr(), n, int(require), buf.advantages.data_ptr(),
+                                              buf.row_index.data_ptr(), out.data_ptr(), out[1:].data_ptr(), buf._env._stream()))
+    else:
+        _lib.check(L.skyjo_vec_rollout_select_seats(buf._env._h, buf.records.data_ptr(), _lib.REC_TILE_PLANAR if buf.planar else _lib.REC_ROW_MAJOR,
+                                                    buf.T, buf.target_flags.data_ptr(), int(require), mask, buf.advantages.data_ptr(),
+                                                    buf.row_index.data_ptr(), out.data_ptr(), out[1:].data_ptr(), buf._env._stream()))
     host = out.cpu()
     count = int(host[0])
     s, q = (float(x) for x in host[1:].view(torch.float64))
@@ -203,12 +226,16 @@ def gather_rows(buf, index, normalize=None, out=None):
     return out if out.actions.shape[0] == m else Minibatch(*(c[:m] for c in out))
 
 
-def minibatches(buf, size, generator=None, normalize=True, require=_lib.TGT_HAS_TARGET, selection=None):
+def minibatches(buf, size, generator=None, normalize=True, require=_lib.TGT_HAS_TARGET, selection=None, seats=None):
     """One epoch over the selected rows in shuffled minibatches: ``select_rows`` (or a ``selection`` made earlier), a
     ``torch.randperm`` of it (``generator``: a generator on the buffer's device), and ``gather_rows`` per slice of ``size`` rows into
     ONE ``Minibatch`` that every step refills - use a batch before asking for the next.  The last slice may be short.
-    ``normalize``: True - the selection's (mean, std), a std of 0 counting as 1; ``(mean, std)``; or None / False."""
-    sel = select_rows(buf, require) if selection is None else selection
+    ``normalize``: True - the selection's (mean, std), a std of 0 counting as 1; ``(mean, std)``; or None / False.  ``seats``: as for
+    ``select_rows`` - the rows of these seats only, normalised with their own moments (``ValueError`` next to a ``selection``, which
+    has chosen its rows already)."""
+    if seats is not None and selection is not None:
+        raise ValueError("seats belongs to the selection: pass select_rows(buf, require, seats=...) as selection, or seats alone")
+    sel = (select_rows(buf, require) if seats is None else select_rows(buf, require, seats=seats)) if selection is None else selection
     if normalize is True:
         normalize = (sel.mean, sel.std if sel.std > 0.0 else 1.0)
     elif normalize is False:
