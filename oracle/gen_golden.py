@@ -35,6 +35,10 @@ inputs -> outputs of the hot path:
                    chosen action among the legal ones, counted by the number of legal actions.  The on-device policy
                    (a different random stream by construction) is held to these distributions (tests/test_gpu_policy_stats.py)
 
+  scoring_order.npz the reference's two scoring functions where the ORDER of their float64 operations shows: _evaluate_game and
+                   _calc_final_rewards on chosen end hands for N = 1 .. 12 under the penalties 2, 1.3, 1/3 and 0.01, and
+                   _calc_final_rewards on arbitrary float64 score vectors (gen_scoring; tests/test_scoring_order.py)
+
 The fixtures are data (inputs and expected outputs) - no reference source text is stored.
 """
 import itertools
@@ -636,7 +640,78 @@ def gen_policy_stats(games=6000):
     return {f"N{N}": (float(out[f"N{N}_ep_len"].mean()), float(out[f"N{N}_refunded"].sum(1).mean())) for N in (2, 3, 4)}
 
 
+SCORING_PENALTIES = [2.0, 1.3, 1.0 / 3.0, 0.01]
+SCORING_REWARD_CFGS = [(1.0, 0.001), (0.1, 0.007), (1.0 / 3.0, 0.0), (-1.0, 0.01)]  # (mean_reward, reward_refunded)
+
+
+def _scoring_hands(rng, N, E):
+    """End hands int8 [E, N, 12], values -2 .. 12: random cards, some columns three equal cards (skipped at scoring,
+    skyjo.py:492), some rows all equal (score 0), some rows from {-2, -1, 0} (negative totals)."""
+    hands = rng.integers(-2, 13, size=(E, N, 12)).astype(np.int8)
+    for e in range(E):
+        for p in range(N):
+            u = rng.random()
+            if u < 0.08:
+                hands[e, p, :] = rng.integers(-2, 13)
+            elif u < 0.25:
+                hands[e, p, :] = rng.integers(-2, 1, size=12)
+            for c in range(4):
+                if rng.random() < 0.15:
+                    hands[e, p, 3 * c:3 * c + 3] = rng.integers(-2, 13)
+    return hands
+
+
+def gen_scoring(seed=5, e_small=14, e_large=24, f_rows=8):
+    """scoring_order.npz: SkyjoGame._evaluate_game (skyjo.py:477-498) and SimpleSkyjoEnv._calc_final_rewards (skyjo_env.py:293-312)
+    called on hands and score vectors chosen so that the ORDER of the float64 operations shows: non-dyadic penalties (1.3, 1/3, 0.01
+    next to 2.0) make the penalised finisher's score inexact, and from eight players on np.mean's pairwise sum differs from the
+    left-to-right one.  Per N = 1 .. 12 (E = e_small hands below eight players, e_large from eight on):
+      N{n}_hands int8 [E, N, 12], N{n}_finisher int32 [E], N{n}_refunded int32 [E, N] (0 .. 4),
+      N{n}_scores float64 [P, E, N] per penalty, N{n}_rewards float64 [P, E, N] - hand e under penalty k with reward pair
+      N{n}_cfg[k, e] (every pair under every penalty, E / 4 hands each),
+      N{n}_fscores float64 [F, N]: arbitrary score vectors (magnitudes 1e-3 .. 1e6, both signs) for _calc_final_rewards alone,
+      N{n}_frefunded int32 [F, N], N{n}_frewards float64 [R, F, N] per reward pair.
+    E and F are what the size limit allows (float64 rewards do not compress; the file may not exceed the largest fixture there is).
+    The seed is one at which every N rejects each wrong order of tests/test_scoring_order.py: a fused multiply-add in the sum shows in
+    about one penalised row in twenty only, so of the seeds 0 .. 39 a handful qualify, 5 being the first."""
+    rng = np.random.default_rng(seed)
+    out = dict(penalties=np.asarray(SCORING_PENALTIES, dtype=np.float64), reward_cfgs=np.asarray(SCORING_REWARD_CFGS, dtype=np.float64),
+               players=np.arange(1, 13, dtype=np.int32))
+    P, R = len(SCORING_PENALTIES), len(SCORING_REWARD_CFGS)
+    for N in range(1, 13):
+        E = e_small if N < 8 else e_large
+        hands = _scoring_hands(rng, N, E)
+        finisher = rng.integers(0, N, size=E).astype(np.int32)
+        refunded = rng.integers(0, 5, size=(E, N)).astype(np.int32)
+        scores = np.zeros((P, E, N), dtype=np.float64)
+        rewards = np.zeros((P, E, N), dtype=np.float64)
+        cfg = np.zeros((P, E), dtype=np.int32)
+        for k, pen in enumerate(SCORING_PENALTIES):
+            for e in range(E):
+                sc = SkyjoGame._evaluate_game(hands[e].copy(), int(finisher[e]), pen)
+                scores[k, e] = np.asarray(sc, dtype=np.float64)
+                cfg[k, e] = (e + k) % R
+                mr, rr = SCORING_REWARD_CFGS[cfg[k, e]]
+                rewards[k, e] = calc_rewards([float(x) for x in sc], [int(x) for x in refunded[e]], mr, rr)
+        fscores = (10.0 ** rng.uniform(-3, 6, size=(f_rows, N)) * rng.choice([-1.0, 1.0], size=(f_rows, N))).astype(np.float64)
+        frefunded = rng.integers(0, 5, size=(f_rows, N)).astype(np.int32)
+        frewards = np.stack([np.stack([calc_rewards([float(x) for x in fscores[f]], [int(x) for x in frefunded[f]], mr, rr)
+                                       for f in range(f_rows)]) for mr, rr in SCORING_REWARD_CFGS])
+        p = "N%d_" % N
+        out.update({p + "hands": hands, p + "finisher": finisher, p + "refunded": refunded, p + "scores": scores, p + "rewards": rewards,
+                    p + "cfg": cfg, p + "fscores": fscores, p + "frefunded": frefunded, p + "frewards": frewards})
+    path = os.path.join(OUT, "scoring_order.npz")
+    np.savez_compressed(path, **out)
+    size = os.path.getsize(path)
+    largest = max(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT) if f != "scoring_order.npz")
+    assert size <= largest, (size, largest)
+    return size
+
+
 def main():
+    if "--scoring-only" in sys.argv:
+        print("scoring_order bytes", gen_scoring())
+        return
     if "--policy-stats-only" in sys.argv:
         print("policy_stats", gen_policy_stats())
         return
@@ -675,6 +750,7 @@ def main():
     print("render", gen_render())
     print("global", gen_global())
     print("policy_stats", gen_policy_stats())
+    print("scoring_order bytes", gen_scoring())
     sz = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("golden bytes", sz)
 

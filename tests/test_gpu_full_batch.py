@@ -141,11 +141,18 @@ def test_every_game_of_the_batch_against_the_oracle(name, B, N, ind, rng_mode, g
         # (freshly seeded games end their first episodes within a few iterations of each other; over a dozen episodes per game a
         # handful of banks can run dry - 3 of 32 768 at S = 2 - and deal in place: slower, same records, which is what was compared)
         assert c["waits"] <= max(16, B // 2048), (name, c["waits"])
-    # final rewards of the games that stand finished right now (float64, ==)
+    # final rewards and scores of the games that stand finished (float64, ==).  Episodes end on one iteration parity only (a draw and a
+    # place alternate, a re-deal takes one iteration) and every launch here is an even number of iterations, so none does yet: one
+    # more iteration, and the games that ended in it stand finished
+    eng.rollout(1, policy_seed=1)
+    ora.rollout(1, 1, threads=THREADS)
     dn = ora.dones.astype(bool)
+    print(f"{name}: {int(dn.sum())} games stand finished")
+    assert dn.sum() > 0
     rew, sc, done = eng.rewards_host()
     np.testing.assert_array_equal(done.astype(bool), dn)
     np.testing.assert_array_equal(rew[dn], ora.rewards[dn])
+    np.testing.assert_array_equal(sc[dn], np.array([[ora.game(int(i)).final_score[p] for p in range(N)] for i in np.flatnonzero(dn)]))
     eng.close()
 
 

@@ -200,9 +200,22 @@ def test_rollout_vs_oracle(N, ind, rng_mode, B):
         assert c[k] == oc[k] if k != "iters" else c[k] == oc["iter"], (k, c, oc)
     # "waits" counts deals made on the in-kernel slow path (pre-dealt episode invalidated by a reshuffle)
     assert c["illegal"] == 0 and c["episodes"] > B and (N > 4 or c["waits"] == 0)
+    # episodes end on one iteration parity only (a draw and a place alternate, a re-deal takes one iteration) and K is even: no game
+    # stands finished now.  One more iteration, and the games that ended in it do.  (128 twelve-player games end about once in three
+    # iterations: there two more iterations at a time until the oracle shows one - eleven times, as it happens.)
+    eng.rollout(1, policy_seed=4242)
+    ora.rollout(1, 4242)
+    for _ in range(32):
+        if ora.dones.any():
+            break
+        eng.rollout(2, policy_seed=4242)
+        ora.rollout(2, 4242)
     dn = ora.dones.astype(bool)
+    print(f"N={N} B={B}: {int(dn.sum())} games stand finished")
+    assert dn.sum() > 0
     rew, sc, done = eng.rewards_host()
     np.testing.assert_array_equal(rew[dn], ora.rewards[dn])
+    np.testing.assert_array_equal(sc[dn], np.array([[ora.game(int(i)).final_score[p] for p in range(N)] for i in np.flatnonzero(dn)]))
     eng.close()
 
 
