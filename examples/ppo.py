@@ -12,8 +12,8 @@ import torch
 
 from skyjo_rl_amd._lib import TGT_HAS_TARGET
 from skyjo_rl_amd.action_mask_model import FLOAT_MIN, FusedNet
-from skyjo_rl_amd.learner import STATS, NativeBranch, PPOLossBuffers, ppo_loss
-from skyjo_rl_amd.rollout import compute_targets, minibatches, select_rows
+from skyjo_rl_amd.learner import STATS, STATS_KL, KLCoeff, NativeBranch, PPOLossBuffers, PPOLossKLBuffers, ppo_loss, ppo_loss_kl
+from skyjo_rl_amd.rollout import behaviour_logits, compute_targets, minibatches, select_rows
 
 
 @torch.no_grad()
@@ -124,8 +124,58 @@ def _ppo_update_native_nets(model, buf, optimizer, epochs, minibatch, clip, vf_c
     return {"first": stats[0], "last": stats[-1], "transitions": sel.count}
 
 
+def _ppo_update_kl(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip, native_nets, kl, behaviour_net,
+                   seats=None):
+    """``ppo_update(..., native_loss=True, kl=...)``: the epochs of ``_ppo_update_native_loss`` (or, with ``native_nets``, of
+    ``_ppo_update_native_nets``) with RLlib's KL penalty - ``rollout.behaviour_logits`` once, before the first step changes (and a
+    ``NativeAdam`` re-packs) the net that played, then ``minibatches(behaviour=True)`` and ``learner.ppo_loss_kl``.  The coefficient
+    is constant during the call; a ``KLCoeff`` is updated once, after the last epoch, from the row-weighted mean ``action_kl`` over
+    every minibatch of the call (as RLlib averages its learner statistics over the SGD phase before ``update_kl`` - from memory)."""
+    coeff = float(kl)
+    behaviour_logits(buf, behaviour_net)
+    compute_targets(buf, gamma=gae[0], lam=gae[1])
+    sel = select_rows(buf, TGT_HAS_TARGET, seats=seats)
+    norm = (sel.mean, max(sel.std, 1e-6))
+    dev = buf.actions.device
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    rows = max(min(minibatch, sel.count), 1)
+    out = PPOLossKLBuffers(rows, dev)
+    if native_nets:
+        policy, value_branch = NativeBranch(model.policy, rows), NativeBranch(model.value, rows)
+    stats = []
+    total_kl, total_rows = 0.0, 0  # host floats, from the epochs' reads: no synchronisation of their own
+    for ep in range(epochs):
+        tot = torch.zeros((7,), dtype=torch.float64, device=dev)
+        seen = 0
+        for mb, old_logits in minibatches(buf, minibatch, generator=gen, normalize=norm, selection=sel, behaviour=True):
+            if native_nets:
+                logits, value = policy.forward(mb.observations), value_branch.forward(mb.observations)
+            else:
+                logits, value = model.policy(mb.observations), model.value(mb.observations)
+            res = ppo_loss_kl(logits, value, mb, old_logits, kl_coeff=coeff, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, vf_clip=vf_clip,
+                              out=out)
+            if native_nets:
+                policy.backward(res.grad_logits)
+                value_branch.backward(res.grad_value)
+            else:
+                optimizer.zero_grad(set_to_none=True)
+                torch.autograd.backward([logits, value], [res.grad_logits, res.grad_value])
+            optimizer.step()
+            n = mb.actions.numel()
+            tot += res.stats * n
+            seen += n
+        host = (tot / max(seen, 1)).tolist()  # the epoch's one read
+        total_kl += host[6] * seen
+        total_rows += seen
+        stats.append({k: host[STATS_KL.index(k)] for k in ("policy_loss", "vf_loss", "kl", "entropy", "clip_fraction", "action_kl")})
+    mean_kl = total_kl / max(total_rows, 1)
+    if isinstance(kl, KLCoeff) and total_rows:
+        coeff = kl.update(mean_kl)
+    return {"first": stats[0], "last": stats[-1], "transitions": sel.count, "mean_action_kl": mean_kl, "kl_coeff": coeff}
+
+
 def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_coef=1.0, seed=0, gae=None, native_batches=False,
-               native_loss=False, ent_coef=0.0, vf_clip=None, native_nets=False, seats=None):
+               native_loss=False, ent_coef=0.0, vf_clip=None, native_nets=False, seats=None, kl=None, behaviour_net=None):
     """Clipped-surrogate PPO epochs over the buffer (RLlib defaults: clip_param 0.3, vf_loss_coeff 1.0).  Returns the mean
     losses of the first and the last epoch.  ``gae``: None - Monte-Carlo returns of the episodes that ended inside the buffer
     (``compute_returns``); (gamma, lambda) - advantages, value targets and the row mask of ``rollout.compute_targets`` (one
@@ -138,7 +188,24 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
     ``learner.NativeBranch``'s kernels on the float32 parameters - a minibatch step is then a fixed sequence of native launches.
     ``seats`` (needs ``native_batches``): an iterable of seat numbers - the update runs on the rows in which these seats acted, their
     advantages normalised with their own moments (``rollout.select_rows(buf, seats=...)``): ``model`` is the policy of those seats
-    in a buffer that ``arena.collect`` filled.  None: every row, as before."""
+    in a buffer that ``arena.collect`` filled.  None: every row, as before.  ``kl`` (needs ``native_loss`` and ``behaviour_net``): a
+    float or a ``learner.KLCoeff`` - the loss gains RLlib's KL penalty against the behaviour distribution (``learner.ppo_loss_kl``;
+    RLlib's default coefficient is 0.2, adapted towards ``kl_target`` 0.01 - restated from memory, ray is not installed here), with
+    ``behaviour_net`` the policy ``FusedNet`` that filled the buffer (of the seats being updated, for an arena buffer).  The epoch
+    statistics gain ``action_kl`` and the result ``mean_action_kl`` - the row-weighted mean over every minibatch of the call - and
+    ``kl_coeff``: the coefficient AFTER the call, a ``KLCoeff`` having been updated once with that mean.  None: no such term, the
+    paths above."""
+    if kl is not None:
+        if isinstance(kl, bool) or not isinstance(kl, (int, float, KLCoeff)):
+            raise ValueError("kl must be None, a float or a learner.KLCoeff")
+        if not native_loss or not native_batches or gae is None:
+            raise ValueError("kl needs native_batches=True, native_loss=True and gae=(gamma, lambda)")
+        if not isinstance(behaviour_net, FusedNet):
+            raise ValueError("kl needs behaviour_net: the policy FusedNet that filled the buffer")
+        return _ppo_update_kl(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip, native_nets, kl,
+                              behaviour_net, seats=seats)
+    if behaviour_net is not None:
+        raise ValueError("behaviour_net belongs to kl")
     if seats is not None and not native_batches:
         raise ValueError("seats belongs to native_batches=True")
     if native_nets and not native_loss:
@@ -201,7 +268,7 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
     return {"first": stats[0], "last": stats[-1], "transitions": int(idx.numel())}
 
 
-def ppo_update_per_seat(models, buf, optimizers, gae=(0.99, 1.0), native_loss=True, native_nets=False, **kw):
+def ppo_update_per_seat(models, buf, optimizers, gae=(0.99, 1.0), native_loss=True, native_nets=False, kls=None, behaviour_nets=None, **kw):
     """One PPO update per seat that has a model, on a buffer ``arena.collect`` filled with every seat playing its own policy - the
     reference's set-up, ``policies = {name: ... for name in env.agents}`` with ``policy_mapping_fn = lambda agent_id: agent_id``
     (``rlskyjo/models/train_model_simple_rllib.py:43-49``).  ``models`` / ``optimizers``: ``buf.N`` entries each, seat s's
@@ -209,7 +276,9 @@ def ppo_update_per_seat(models, buf, optimizers, gae=(0.99, 1.0), native_loss=Tr
     seat that does not learn (a frozen or a random opponent).  Seat s runs ``ppo_update(models[s], buf, optimizers[s], seats=(s,),
     native_batches=True, ...)``: its own rows, normalised with its own moments, as RLlib normalises per policy batch.  Seats that
     share a model must be updated together: call ``ppo_update(..., seats=(s0, s1))`` yourself.  Returns the list of ``ppo_update``'s
-    results, None for a seat without a model.  ``kw``: ``ppo_update``'s other keywords."""
+    results, None for a seat without a model.  ``kls`` / ``behaviour_nets``: ``buf.N`` entries each - seat s's ``kl`` (a float or its own
+    ``learner.KLCoeff``) and the policy ``FusedNet`` that played it -, None where the seat does not learn or learns without the
+    penalty; both None: no seat has one.  ``kw``: ``ppo_update``'s other keywords."""
     models, optimizers = list(models), list(optimizers)
     if len(models) != buf.N or len(optimizers) != buf.N:
         raise ValueError(f"models and optimizers need {buf.N} entries each (None for a seat that does not learn)")
@@ -218,8 +287,14 @@ def ppo_update_per_seat(models, buf, optimizers, gae=(0.99, 1.0), native_loss=Tr
     learners = [m for m in models if m is not None]
     if len({id(m) for m in learners}) != len(learners):
         raise ValueError("two seats share a model: update them in one ppo_update(..., seats=(...)) call")
+    kls = [None] * buf.N if kls is None else list(kls)
+    behaviour_nets = [None] * buf.N if behaviour_nets is None else list(behaviour_nets)
+    if len(kls) != buf.N or len(behaviour_nets) != buf.N:
+        raise ValueError(f"kls and behaviour_nets need {buf.N} entries each (None for a seat without the KL penalty)")
+    if any(m is None and (k is not None or b is not None) for m, k, b in zip(models, kls, behaviour_nets)):
+        raise ValueError("a seat without a model takes neither a kl nor a behaviour_net")
     return [None if m is None else ppo_update(m, buf, o, gae=gae, native_batches=True, native_loss=native_loss, native_nets=native_nets,
-                                              seats=(s,), **kw)
+                                              seats=(s,), kl=kls[s], behaviour_net=behaviour_nets[s], **kw)
             for s, (m, o) in enumerate(zip(models, optimizers))]
 
 

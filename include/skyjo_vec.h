@@ -527,10 +527,18 @@ int skyjo_vec_rollout_gather(skyjo_vec *h, const void *records, int32_t layout, 
                              const float *advantages, const float *value_targets, float adv_mean, float adv_std,
                              float *obs_out, float *logmask_out, int64_t *actions_out, float *logp_out, float *advantages_out,
                              float *value_targets_out, float *values_out, uint8_t *seats_out, void *stream);
+/* skyjo_vec_rollout_gather_logits: the rows index[0 .. m) of a float32 [n_rows][26] column that lies beside the buffer - the behaviour
+ * policy's logits, one row per row id r = t * num_envs + b (skyjo_vec_rollout_buffers has no such column, and skyjo_vec_rollout_gather no
+ * such output) - as out float32 [m][26], 16-byte aligned, one kernel.  The contract of skyjo_vec_rollout_gather: any order, repeats
+ * allowed, m == 0 is no work, a row id outside [0, n_rows) reads nothing and gives an all-zero row.  Needs no handle: it runs on the
+ * current device, on `stream`.  SKYJO_E_INVALID (nothing is launched): a null pointer, a negative m or n_rows, an out that is not 16-byte
+ * aligned, a column or an index that is not aligned to its element size. */
+int skyjo_vec_rollout_gather_logits(const float *column /* [n_rows][26] */, int64_t n_rows, const int64_t *index, int64_t m,
+                                    float *out /* [m][26], 16-byte aligned */, void *stream);
 
 /* The PPO loss head of a learner minibatch, on device: everything between a model's two outputs and optimizer.step() - the masked
  * softmax of action_mask_model.py:58-74, the clipped surrogate, the value loss and the entropy of the PPO the reference trains with
- * (rlskyjo/models/train_model_simple_rllib.py:54-57) - in one kernel that reads every input once and writes the gradients with
+ * (rlskyjo/models/train_model_simple_rllib.py:54-57; without the KL penalty of RLlib's default loss: skyjo_vec_ppo_loss_kl below) - in one kernel that reads every input once and writes the gradients with
  * respect to the logits and the value, plus a single-workgroup launch that finishes the statistics.  Needs no engine handle: it runs
  * on the current device, on `stream`.  All arrays are dense device arrays of m >= 1 rows:
  *   logits         float32 [m][26]  the policy branch's raw output; 16-byte aligned
@@ -558,6 +566,32 @@ int skyjo_vec_ppo_loss(const float *logits, const float *log_mask, const float *
                        const float *advantages, const float *value_targets, const float *values_old, int64_t m, float clip,
                        float vf_coef, float ent_coef, float vf_clip, float *grad_logits_out, float *grad_value_out,
                        double *stats_out /* device, 6 */, void *scratch, int64_t scratch_bytes, void *stream);
+/* skyjo_vec_ppo_loss_kl: the same head with the KL penalty of RLlib's default PPO loss, which the reference's script leaves switched on
+ * (ppo.DEFAULT_CONFIG untouched: kl_coeff 0.2, kl_target 0.01) - the divergence of the new masked distribution from the BEHAVIOUR
+ * policy's whole masked distribution, not the sampled estimate `kl` above.  ray is not installed where this library is developed: the
+ * form of the term is restated from memory of RLlib 1.9's torch policy, not checked against it.  The arguments, the definitions and the
+ * promises of skyjo_vec_ppo_loss, and:
+ *   old_logits     float32 [m][26]  the behaviour policy's raw logits of the rows (skyjo_vec_rollout_gather_logits); 16-byte aligned
+ *   kl_coeff       finite, >= 0
+ * Per row, in float32, beside the above:  zo = old_logits + log_mask;  Mo = max zo;  So = sum exp(zo - Mo);  logpo = zo - Mo - log So;
+ * po = exp(zo - Mo) / So;
+ *   akl = sum over k with po_k > 0 of po_k (logpo_k - logp_k)      KL(pi_old || pi_new); logp_k is finite wherever the action is legal,
+ *                                                                  also where p_k underflowed to 0
+ * L = 1/m sum (pl + vf_coef vl - ent_coef H + kl_coeff akl).  The outputs:
+ *   grad_logits_out   as above, plus 1/m kl_coeff (p_k - po_k) - 0 at a masked k, where p_k == po_k == 0: the masked k != action still gets
+ *                     exactly 0.0.  With kl_coeff == 0 nothing is added: the bits of skyjo_vec_ppo_loss
+ *   grad_value_out    as above
+ *   stats_out         double [7]: the six above - the loss with the new term; with kl_coeff == 0 the bits of skyjo_vec_ppo_loss - and
+ *                     action_kl, the mean of akl, computed whatever kl_coeff is (a coefficient can adapt from 0)
+ *   scratch           at least skyjo_vec_ppo_loss_kl_scratch_bytes(m) bytes
+ * A row with one legal action has p = po = 1: akl == 0.0 and a KL gradient term of 0.0, both exactly.  The same input gives the same
+ * bits on every call.  SKYJO_E_INVALID as for skyjo_vec_ppo_loss, and on a null or misaligned old_logits and a kl_coeff that is
+ * negative or not finite. */
+int64_t skyjo_vec_ppo_loss_kl_scratch_bytes(int64_t m); /* 0 for m < 1 */
+int skyjo_vec_ppo_loss_kl(const float *logits, const float *log_mask, const float *old_logits, const float *value, const int64_t *actions,
+                          const float *logp_old, const float *advantages, const float *value_targets, const float *values_old, int64_t m,
+                          float clip, float vf_coef, float ent_coef, float vf_clip, float kl_coeff, float *grad_logits_out,
+                          float *grad_value_out, double *stats_out /* device, 7 */, void *scratch, int64_t scratch_bytes, void *stream);
 
 /* One branch of the model - Linear(obs_dim, 256) - tanh - Linear(256, 256) - tanh - Linear(256, out_dim), 1 <= obs_dim <= 31,
  * 1 <= out_dim <= 32: skyjo_vec_mlp_create's limits - trained on its float32 master parameters, on device: the forward that keeps its

@@ -124,6 +124,10 @@ SIGNATURES = {
     "skyjo_vec_ppo_loss_scratch_bytes": (I64, [I64]),
     "skyjo_vec_ppo_loss": (C.c_int, [VP, VP, VP, VP, VP, VP, VP, VP, I64, C.c_float, C.c_float, C.c_float, C.c_float, VP, VP, VP,
                                      VP, I64, VP]),
+    "skyjo_vec_rollout_gather_logits": (C.c_int, [VP, I64, VP, I64, VP, VP]),
+    "skyjo_vec_ppo_loss_kl_scratch_bytes": (I64, [I64]),
+    "skyjo_vec_ppo_loss_kl": (C.c_int, [VP, VP, VP, VP, VP, VP, VP, VP, VP, I64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                        VP, VP, VP, VP, I64, VP]),
     "skyjo_vec_mlp_train_workspace_bytes": (I64, [I32, I32, I64]),
     "skyjo_vec_mlp_train_forward": (C.c_int, [I32, I32, VP, VP, I64, VP, VP, I64, VP]),
     "skyjo_vec_mlp_train_backward": (C.c_int, [I32, I32, VP, VP, VP, I64, VP, VP, I64, VP]),

@@ -336,3 +336,44 @@ __global__ __launch_bounds__(SK_GATHER_THREADS) void k_gather_rows(SkGatherArgs 
     }
   }
 }
+
+// (c) k_gather_logits (skyjo_vec_rollout_gather_logits): rows of a float [n_rows][26] column - the behaviour logits a learner keeps
+//     beside the buffer - by the row ids of k_gather_rows, which knows no such column.  A workgroup owns SK_GATHER_ROWS consecutive
+//     OUTPUT rows: their ids go to LDS once, the run's flat [rows * 26] stretch leaves as 16-byte stores (the run starts at byte
+//     o0 * 104, o0 a multiple of 64), each element read where its row lies (a row starts on an 8-byte boundary only: dword loads).
+//     A row id outside [0, n_rows) reads nothing and gives an all-zero row.
+__global__ __launch_bounds__(SK_GATHER_THREADS) void k_gather_logits(const float *column, long long n_rows, const long long *index, long long m,
+                                                                    float *out) {
+  __shared__ long long rid[SK_GATHER_ROWS];  // -1: id out of range
+  const int tid = threadIdx.x;
+  const long long o0 = (long long)blockIdx.x * SK_GATHER_ROWS;
+  const int rows = m - o0 < SK_GATHER_ROWS ? (int)(m - o0) : SK_GATHER_ROWS;
+  if (tid < SK_GATHER_ROWS) {
+    long long r = -1;
+    if (tid < rows) {
+      const long long x = index[o0 + tid];
+      if (x >= 0 && x < n_rows) r = x;
+    }
+    rid[tid] = r;
+  }
+  __syncthreads();
+  const int total = rows * SKYJO_NUM_ACTIONS;
+  float *dst = out + o0 * SKYJO_NUM_ACTIONS;
+  for (int e = tid * 4; e < total; e += SK_GATHER_THREADS * 4) {
+    int i = e / SKYJO_NUM_ACTIONS, k = e - i * SKYJO_NUM_ACTIONS;
+    float x[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      x[j] = 0.f;
+      if (e + j < total && rid[i] >= 0) x[j] = column[rid[i] * SKYJO_NUM_ACTIONS + k];
+      if (++k == SKYJO_NUM_ACTIONS) k = 0, i++;
+    }
+    if (e + 4 <= total) {
+      *(float4 *)(dst + e) = make_float4(x[0], x[1], x[2], x[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (e + j < total) dst[e + j] = x[j];
+    }
+  }
+}

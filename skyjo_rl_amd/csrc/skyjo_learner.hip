@@ -1,5 +1,5 @@
 // skyjo_learner.hip - the packed nets' handles and the learner behind the extern "C" boundary of include/skyjo_vec.h: skyjo_vec_mlp_*,
-// skyjo_vec_rollout_targets / _select / _gather, skyjo_vec_ppo_loss, skyjo_vec_mlp_train_*, skyjo_vec_arena_* and skyjo_vec_episode_stats,
+// skyjo_vec_rollout_targets / _select / _gather / _gather_logits, skyjo_vec_ppo_loss / _kl, skyjo_vec_mlp_train_*, skyjo_vec_arena_* and skyjo_vec_episode_stats,
 // with their kernels (skyjo_update.h, skyjo_targets.h, skyjo_batches.h, skyjo_loss.h, skyjo_train.h, skyjo_arena.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
 // (skyjo_capi.hip, skyjo_device.h and its parts), and of an engine it sees what skyjo_host.h shows - the record layout, B, G, game_id0,
 // the device and the select scratch.  gfx950 only, no CPU path.
@@ -339,45 +339,86 @@ int skyjo_vec_rollout_gather(skyjo_vec *h, const void *records, int32_t layout, 
   return SKYJO_OK;
 }
 
-// ---- the PPO loss head of a learner minibatch (include/skyjo_vec.h: skyjo_vec_ppo_loss; the kernels: skyjo_loss.h) ----
+int skyjo_vec_rollout_gather_logits(const float *column, int64_t n_rows, const int64_t *index, int64_t m, float *out, void *stream) {
+  if (!column || !index || !out) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather_logits: null argument");
+  if (m < 0 || n_rows < 0) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather_logits: m and n_rows must not be negative");
+  if (!aligned16(out) || ((uintptr_t)column & 3) != 0 || ((uintptr_t)index & 7) != 0)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather_logits: out must be 16-byte aligned, column and index aligned to their element size");
+  if (m == 0) return SKYJO_OK;
+  if (m > (int64_t)SK_GATHER_ROWS * 0x7fffffff) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather_logits: m is out of range");
+  hipLaunchKernelGGL(k_gather_logits, dim3((unsigned)((m + SK_GATHER_ROWS - 1) / SK_GATHER_ROWS)), dim3(SK_GATHER_THREADS), 0, (hipStream_t)stream,
+                     column, (long long)n_rows, (const long long *)index, (long long)m, out);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+// ---- the PPO loss head of a learner minibatch (include/skyjo_vec.h: skyjo_vec_ppo_loss, skyjo_vec_ppo_loss_kl; the kernels: skyjo_loss.h) ----
 static constexpr int64_t kLossMaxRows = (int64_t)SK_LOSS_ROWS * 0x7fffffff;
-int64_t skyjo_vec_ppo_loss_scratch_bytes(int64_t m) {
+static int64_t loss_scratch_bytes(int64_t m, int stats) {
   if (m < 1 || m > kLossMaxRows) return 0;
-  return (m + SK_LOSS_ROWS - 1) / SK_LOSS_ROWS * (int64_t)(SK_LOSS_STATS * sizeof(double));
+  return (m + SK_LOSS_ROWS - 1) / SK_LOSS_ROWS * (int64_t)(stats * sizeof(double));
+}
+int64_t skyjo_vec_ppo_loss_scratch_bytes(int64_t m) { return loss_scratch_bytes(m, SK_LOSS_STATS); }
+int64_t skyjo_vec_ppo_loss_kl_scratch_bytes(int64_t m) { return loss_scratch_bytes(m, SK_LOSS_KL_STATS); }
+
+// both entries: the checks, then the main launch and the finish.  KL: old_logits and kl_coeff take part, seven statistics
+static int ppo_loss(const char *who, const bool KL, const float *logits, const float *log_mask, const float *old_logits, const float *value,
+                    const int64_t *actions, const float *logp_old, const float *advantages, const float *value_targets,
+                    const float *values_old, int64_t m, float clip, float vf_coef, float ent_coef, float vf_clip, float kl_coeff,
+                    float *grad_logits_out, float *grad_value_out, double *stats_out, void *scratch, int64_t scratch_bytes, void *stream) {
+  const std::string name(who);
+  if (!logits || !log_mask || (KL && !old_logits) || !value || !actions || !logp_old || !advantages || !value_targets || !values_old ||
+      !grad_logits_out || !grad_value_out || !stats_out || !scratch)
+    return fail(SKYJO_E_INVALID, name + ": null argument");
+  if (m < 1 || m > kLossMaxRows) return fail(SKYJO_E_INVALID, name + ": m must be at least 1");
+  if (!std::isfinite(clip) || !(clip > 0.f)) return fail(SKYJO_E_INVALID, name + ": clip must be finite and greater than 0");
+  if (!std::isfinite(vf_coef) || !std::isfinite(ent_coef)) return fail(SKYJO_E_INVALID, name + ": vf_coef and ent_coef must be finite");
+  if (KL && (!std::isfinite(kl_coeff) || !(kl_coeff >= 0.f))) return fail(SKYJO_E_INVALID, name + ": kl_coeff must be finite and not negative");
+  if ((((uintptr_t)logits | (uintptr_t)log_mask | (uintptr_t)grad_logits_out) & 15) != 0)
+    return fail(SKYJO_E_INVALID, name + ": logits, log_mask and grad_logits_out must be 16-byte aligned");
+  if (KL && !aligned16(old_logits)) return fail(SKYJO_E_INVALID, name + ": old_logits must be 16-byte aligned");
+  if ((((uintptr_t)value | (uintptr_t)logp_old | (uintptr_t)advantages | (uintptr_t)value_targets | (uintptr_t)values_old |
+        (uintptr_t)grad_value_out) & 3) != 0 || (((uintptr_t)actions | (uintptr_t)stats_out | (uintptr_t)scratch) & 7) != 0)
+    return fail(SKYJO_E_INVALID, name + ": a column, stats_out or scratch is not aligned to its element size");
+  const int NS = KL ? SK_LOSS_KL_STATS : SK_LOSS_STATS;
+  if (scratch_bytes < loss_scratch_bytes(m, NS)) return fail(SKYJO_E_INVALID, name + ": scratch is smaller than " + name + "_scratch_bytes(m)");
+  static_assert(SK_LOSS_ROWS % 2 == 0 && SK_LOSS_ROWS <= SK_LOSS_THREADS, "a run is whole 16-byte pieces and every row has its lane");
+  SkLossArgs a{};
+  a.logits = logits, a.log_mask = log_mask, a.old_logits = old_logits, a.value = value, a.actions = (const long long *)actions;
+  a.logp_old = logp_old, a.adv = advantages, a.vt = value_targets, a.v_old = values_old, a.g_logits = grad_logits_out, a.g_value = grad_value_out;
+  a.partial = (double *)scratch, a.m = m;
+  a.lo = (float)(1.0 - (double)clip), a.hi = (float)(1.0 + (double)clip);
+  a.vf_coef = vf_coef, a.ent_coef = ent_coef;
+  a.vf_clip = (std::isfinite(vf_clip) && vf_clip > 0.f) ? vf_clip : 0.f;
+  a.inv_m = 1.0f / (float)m;
+  a.kl_coeff = kl_coeff;
+  const int64_t nb = (m + SK_LOSS_ROWS - 1) / SK_LOSS_ROWS;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)nb), one(1), threads(SK_LOSS_THREADS), fin(SK_LOSS_FIN_THREADS);
+  if (KL) hipLaunchKernelGGL(k_ppo_loss<true>, grid, threads, 0, s, a);
+  else hipLaunchKernelGGL(k_ppo_loss<false>, grid, threads, 0, s, a);
+  HIPCHK(hipGetLastError());
+  if (KL) hipLaunchKernelGGL(k_ppo_loss_finish<SK_LOSS_KL_STATS>, one, fin, 0, s, (const double *)scratch, (int)nb, (double)m, stats_out);
+  else hipLaunchKernelGGL(k_ppo_loss_finish<SK_LOSS_STATS>, one, fin, 0, s, (const double *)scratch, (int)nb, (double)m, stats_out);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
 }
 
 int skyjo_vec_ppo_loss(const float *logits, const float *log_mask, const float *value, const int64_t *actions, const float *logp_old,
                        const float *advantages, const float *value_targets, const float *values_old, int64_t m, float clip,
                        float vf_coef, float ent_coef, float vf_clip, float *grad_logits_out, float *grad_value_out, double *stats_out,
                        void *scratch, int64_t scratch_bytes, void *stream) {
-  if (!logits || !log_mask || !value || !actions || !logp_old || !advantages || !value_targets || !values_old || !grad_logits_out ||
-      !grad_value_out || !stats_out || !scratch)
-    return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: null argument");
-  if (m < 1 || m > kLossMaxRows) return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: m must be at least 1");
-  if (!std::isfinite(clip) || !(clip > 0.f)) return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: clip must be finite and greater than 0");
-  if (!std::isfinite(vf_coef) || !std::isfinite(ent_coef)) return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: vf_coef and ent_coef must be finite");
-  if ((((uintptr_t)logits | (uintptr_t)log_mask | (uintptr_t)grad_logits_out) & 15) != 0)
-    return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: logits, log_mask and grad_logits_out must be 16-byte aligned");
-  if ((((uintptr_t)value | (uintptr_t)logp_old | (uintptr_t)advantages | (uintptr_t)value_targets | (uintptr_t)values_old |
-        (uintptr_t)grad_value_out) & 3) != 0 || (((uintptr_t)actions | (uintptr_t)stats_out | (uintptr_t)scratch) & 7) != 0)
-    return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: a column, stats_out or scratch is not aligned to its element size");
-  if (scratch_bytes < skyjo_vec_ppo_loss_scratch_bytes(m)) return fail(SKYJO_E_INVALID, "skyjo_vec_ppo_loss: scratch is smaller than skyjo_vec_ppo_loss_scratch_bytes(m)");
-  static_assert(SK_LOSS_ROWS % 2 == 0 && SK_LOSS_ROWS <= SK_LOSS_THREADS, "a run is whole 16-byte pieces and every row has its lane");
-  SkLossArgs a{};
-  a.logits = logits, a.log_mask = log_mask, a.value = value, a.actions = (const long long *)actions, a.logp_old = logp_old;
-  a.adv = advantages, a.vt = value_targets, a.v_old = values_old, a.g_logits = grad_logits_out, a.g_value = grad_value_out;
-  a.partial = (double *)scratch, a.m = m;
-  a.lo = (float)(1.0 - (double)clip), a.hi = (float)(1.0 + (double)clip);
-  a.vf_coef = vf_coef, a.ent_coef = ent_coef;
-  a.vf_clip = (std::isfinite(vf_clip) && vf_clip > 0.f) ? vf_clip : 0.f;
-  a.inv_m = 1.0f / (float)m;
-  const int64_t nb = (m + SK_LOSS_ROWS - 1) / SK_LOSS_ROWS;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_ppo_loss, dim3((unsigned)nb), dim3(SK_LOSS_THREADS), 0, s, a);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_ppo_loss_finish, dim3(1), dim3(SK_LOSS_FIN_THREADS), 0, s, (const double *)scratch, (int)nb, (double)m, stats_out);
-  HIPCHK(hipGetLastError());
-  return SKYJO_OK;
+  return ppo_loss("skyjo_vec_ppo_loss", false, logits, log_mask, nullptr, value, actions, logp_old, advantages, value_targets, values_old, m,
+                         clip, vf_coef, ent_coef, vf_clip, 0.f, grad_logits_out, grad_value_out, stats_out, scratch, scratch_bytes, stream);
+}
+
+int skyjo_vec_ppo_loss_kl(const float *logits, const float *log_mask, const float *old_logits, const float *value, const int64_t *actions,
+                          const float *logp_old, const float *advantages, const float *value_targets, const float *values_old, int64_t m,
+                          float clip, float vf_coef, float ent_coef, float vf_clip, float kl_coeff, float *grad_logits_out,
+                          float *grad_value_out, double *stats_out, void *scratch, int64_t scratch_bytes, void *stream) {
+  return ppo_loss("skyjo_vec_ppo_loss_kl", true, logits, log_mask, old_logits, value, actions, logp_old, advantages, value_targets,
+                        values_old, m, clip, vf_coef, ent_coef, vf_clip, kl_coeff, grad_logits_out, grad_value_out, stats_out, scratch,
+                        scratch_bytes, stream);
 }
 
 // ---- a branch's training forward and backward on its float32 parameters (include/skyjo_vec.h: skyjo_vec_mlp_train_*; skyjo_train.h) ----

@@ -14,6 +14,12 @@
 // (b) k_ppo_loss_finish, ONE workgroup: thread t owns a contiguous span of blocks, then the wavefront's tree, then the wavefronts in
 //     order (k_select_scan's order), divided by m: stats[0 .. 5] = loss, policy_loss, vf_loss, entropy, kl, clip_fraction.
 //     The same input gives the same bits on every call.
+// (c) k_ppo_loss<true> (skyjo_vec_ppo_loss_kl) adds the KL penalty against the behaviour distribution.  A SECOND image at the same
+//     stride holds zo = old_logits + log_mask (13 824 bytes more, fetched by the same 16-byte walk).  The lane streams its old row
+//     out of LDS - once for the maximum, once for the sum, once inside the gradient loop, where po_k and logpo_k are formed, used
+//     and dropped - instead of holding a third 26-float array in registers: still no private segment.  A seventh statistic,
+//     action_kl, follows the six.  k_ppo_loss<false> is the kernel of (a), statement for statement: every addition sits behind
+//     `if constexpr (KL)`, and with kl_coeff == 0 the <true> form adds nothing to a gradient or to the loss - the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,25 +31,31 @@
 #define SK_LOSS_WAVES (SK_LOSS_THREADS / 64)
 #define SK_LOSS_STRIDE 27    // dwords between the rows of the LDS image (odd: conflict-free for one lane per row)
 #define SK_LOSS_STATS 6
+#define SK_LOSS_KL_STATS 7   // ... and action_kl
 #define SK_LOSS_FIN_THREADS 1024
 
 struct SkLossArgs {
   const float *logits, *log_mask;  // [m][26], 16-byte aligned
+  const float *old_logits;         // [m][26], 16-byte aligned (k_ppo_loss<true> only)
   const float *value;              // [m]
   const long long *actions;        // [m], each in [0, 26)
   const float *logp_old, *adv, *vt, *v_old;
   float *g_logits;                 // [m][26], 16-byte aligned
   float *g_value;                  // [m]
-  double *partial;                 // [blocks][6]
+  double *partial;                 // [blocks][6], <true>: [blocks][7]
   long long m;
   float lo, hi;                    // 1 - clip, 1 + clip (rounded once from double)
   float vf_coef, ent_coef, vf_clip;  // vf_clip <= 0: no value clipping
   float inv_m;
+  float kl_coeff;                  // >= 0 (k_ppo_loss<true> only)
 };
 
+template <bool KL>
 __global__ __launch_bounds__(SK_LOSS_THREADS) void k_ppo_loss(SkLossArgs a) {
+  constexpr int NS = KL ? SK_LOSS_KL_STATS : SK_LOSS_STATS;
   __shared__ float zs[SK_LOSS_ROWS * SK_LOSS_STRIDE];
-  __shared__ double wsum[SK_LOSS_WAVES][SK_LOSS_STATS];
+  __shared__ float zos[KL ? SK_LOSS_ROWS * SK_LOSS_STRIDE : 1];  // the old rows' image (unused, and dropped, without KL)
+  __shared__ double wsum[SK_LOSS_WAVES][NS];
   constexpr int K = SKYJO_NUM_ACTIONS;
   const int tid = threadIdx.x;
   const long long o0 = (long long)blockIdx.x * SK_LOSS_ROWS;
@@ -52,30 +64,40 @@ __global__ __launch_bounds__(SK_LOSS_THREADS) void k_ppo_loss(SkLossArgs a) {
 
   {  // z = logits + log_mask into the image
     const float *lg = a.logits + o0 * K, *lm = a.log_mask + o0 * K;
+    [[maybe_unused]] const float *ol = KL ? a.old_logits + o0 * K : nullptr;
     for (int e = tid * 4; e < total; e += SK_LOSS_THREADS * 4) {
       float x[4], y[4];
+      [[maybe_unused]] float xo[4];
       if (e + 4 <= total) {
         const float4 u = *(const float4 *)(lg + e), v = *(const float4 *)(lm + e);
         x[0] = u.x, x[1] = u.y, x[2] = u.z, x[3] = u.w;
         y[0] = v.x, y[1] = v.y, y[2] = v.z, y[3] = v.w;
+        if constexpr (KL) {
+          const float4 w = *(const float4 *)(ol + e);
+          xo[0] = w.x, xo[1] = w.y, xo[2] = w.z, xo[3] = w.w;
+        }
       } else {
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           x[j] = e + j < total ? lg[e + j] : 0.f;
           y[j] = e + j < total ? lm[e + j] : 0.f;
+          if constexpr (KL) xo[j] = e + j < total ? ol[e + j] : 0.f;
         }
       }
       int i = e / K, k = e - i * K;
 #pragma unroll
       for (int j = 0; j < 4; j++) {
-        if (e + j < total) zs[i * SK_LOSS_STRIDE + k] = x[j] + y[j];
+        if (e + j < total) {
+          zs[i * SK_LOSS_STRIDE + k] = x[j] + y[j];
+          if constexpr (KL) zos[i * SK_LOSS_STRIDE + k] = xo[j] + y[j];
+        }
         if (++k == K) k = 0, i++;
       }
     }
   }
   __syncthreads();
 
-  double st[SK_LOSS_STATS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double st[NS] = {};
   if (tid < rows) {
     const long long o = o0 + tid;
     float *zr = zs + tid * SK_LOSS_STRIDE;
@@ -113,11 +135,29 @@ __global__ __launch_bounds__(SK_LOSS_THREADS) void k_ppo_loss(SkLossArgs a) {
     float q = 0.f;
 #pragma unroll
     for (int k = 0; k < K; k++) q += k == ai ? 0.f : p[k];
+    // the old distribution's maximum, sum and log-sum; its 26 terms are formed again, one at a time, in the gradient loop
+    [[maybe_unused]] const float *zor = zos + (KL ? tid * SK_LOSS_STRIDE : 0);
+    [[maybe_unused]] float Mo = 0.f, So = 0.f, logSo = 0.f, akl = 0.f;
+    [[maybe_unused]] const float ks = a.inv_m * a.kl_coeff;
+    if constexpr (KL) {
+      Mo = zor[0];
+#pragma unroll
+      for (int k = 1; k < K; k++) Mo = fmaxf(Mo, zor[k]);
+#pragma unroll
+      for (int k = 0; k < K; k++) So += expf(zor[k] - Mo);
+      logSo = logf(So);
+    }
 #pragma unroll
     for (int k = 0; k < K; k++) {
       float g = k == ai ? -(gs * q) : gs * p[k];
       if (p[k] > 0.f) g += es * (p[k] * (z[k] + H));
       else if (k != ai) g = 0.f;
+      if constexpr (KL) {
+        // po_k == 0 exactly at a masked k (as p_k): no term there; z[k] = logp_k is finite wherever po_k > 0, also where p_k is 0
+        const float zo = zor[k] - Mo, po = expf(zo) / So;
+        if (po > 0.f) akl += po * ((zo - logSo) - z[k]);
+        if (a.kl_coeff != 0.f) g += ks * (p[k] - po);
+      }
       zr[k] = g;
     }
     const float d1 = v - vt;
@@ -134,18 +174,22 @@ __global__ __launch_bounds__(SK_LOSS_THREADS) void k_ppo_loss(SkLossArgs a) {
     st[0] = (st[1] + (double)a.vf_coef * st[2]) - (double)a.ent_coef * st[3];
     st[4] = (double)lp_old - (double)lp;
     st[5] = clipped ? 1.0 : 0.0;
+    if constexpr (KL) {
+      st[6] = (double)akl;
+      if (a.kl_coeff != 0.f) st[0] += (double)a.kl_coeff * st[6];
+    }
   }
 #pragma unroll
-  for (int j = 0; j < SK_LOSS_STATS; j++) st[j] = sk_wave_sum(st[j]);
+  for (int j = 0; j < NS; j++) st[j] = sk_wave_sum(st[j]);
   if ((tid & 63) == 0) {
 #pragma unroll
-    for (int j = 0; j < SK_LOSS_STATS; j++) wsum[tid >> 6][j] = st[j];
+    for (int j = 0; j < NS; j++) wsum[tid >> 6][j] = st[j];
   }
   __syncthreads();
-  if (tid < SK_LOSS_STATS) {
+  if (tid < NS) {
     double s = wsum[0][tid];
     for (int w = 1; w < SK_LOSS_WAVES; w++) s += wsum[w][tid];
-    a.partial[(size_t)blockIdx.x * SK_LOSS_STATS + tid] = s;
+    a.partial[(size_t)blockIdx.x * NS + tid] = s;
   }
 
   {  // the gradients, out of the image
@@ -169,25 +213,26 @@ __global__ __launch_bounds__(SK_LOSS_THREADS) void k_ppo_loss(SkLossArgs a) {
   }
 }
 
+template <int NS>  // SK_LOSS_STATS, or SK_LOSS_KL_STATS after k_ppo_loss<true>
 __global__ __launch_bounds__(SK_LOSS_FIN_THREADS) void k_ppo_loss_finish(const double *partial, int nb, double m, double *stats_out) {
-  __shared__ double wsum[SK_LOSS_FIN_THREADS / 64][SK_LOSS_STATS];
+  __shared__ double wsum[SK_LOSS_FIN_THREADS / 64][NS];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int per = (nb + SK_LOSS_FIN_THREADS - 1) / SK_LOSS_FIN_THREADS;
   const long long lo_ = (long long)t * per;
   const int lo = lo_ < nb ? (int)lo_ : nb, hi = lo + per < nb ? lo + per : nb;
-  double s[SK_LOSS_STATS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double s[NS] = {};
   for (int i = lo; i < hi; i++) {
 #pragma unroll
-    for (int j = 0; j < SK_LOSS_STATS; j++) s[j] += partial[(size_t)i * SK_LOSS_STATS + j];
+    for (int j = 0; j < NS; j++) s[j] += partial[(size_t)i * NS + j];
   }
 #pragma unroll
-  for (int j = 0; j < SK_LOSS_STATS; j++) s[j] = sk_wave_sum(s[j]);
+  for (int j = 0; j < NS; j++) s[j] = sk_wave_sum(s[j]);
   if (lane == 0) {
 #pragma unroll
-    for (int j = 0; j < SK_LOSS_STATS; j++) wsum[w][j] = s[j];
+    for (int j = 0; j < NS; j++) wsum[w][j] = s[j];
   }
   __syncthreads();
-  if (t < SK_LOSS_STATS) {
+  if (t < NS) {
     double x = 0.0;
     for (int i = 0; i < SK_LOSS_FIN_THREADS / 64; i++) x += wsum[i][t];
     stats_out[t] = x / m;

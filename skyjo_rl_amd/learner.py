@@ -18,6 +18,16 @@ RLlib's ``vf_clip_param`` form: ``vl = max(vl, (vc - vt)^2)`` with ``vc = v_old 
 installed where this package is developed: that form is restated from memory of RLlib's torch policy, not checked against it (as
 ``action_mask_model.py`` says of ``TorchFC``).  The gradients are the ones torch's autograd gives for the same expression; the
 statistics are means over the rows, accumulated in double in a fixed order - the same input gives the same bits on every call.
+
+``ppo_loss_kl`` (``skyjo_vec_ppo_loss_kl``) is the same head with the term RLlib's DEFAULT PPO loss carries besides - the reference leaves
+``ppo.DEFAULT_CONFIG`` as it is, ``kl_coeff`` 0.2 and ``kl_target`` 0.01 with it::
+
+    L = mean( surrogate + kl_coeff KL(pi_old(.|s) || pi_new(.|s)) + vf_coef vl - ent_coef H )
+
+over the WHOLE masked distributions - which needs the behaviour policy's logits per row (``rollout.behaviour_logits``, gathered by
+``rollout.minibatches(behaviour=True)``), not the ``logp`` of the chosen action the ``kl`` statistic above is estimated from.  Its seventh
+statistic ``action_kl`` is the mean of that divergence; ``KLCoeff`` adapts the coefficient from it after an update: times 1.5 above
+``2 kl_target``, times 0.5 below ``0.5 kl_target``.  The term and the rule are, like ``vf_clip``, restated from memory of RLlib 1.9.
 """
 import ctypes as C
 import math
@@ -29,6 +39,7 @@ from . import _lib
 
 PPOLossResult = namedtuple("PPOLossResult", ["stats", "grad_logits", "grad_value"])
 STATS = ("loss", "policy_loss", "vf_loss", "entropy", "kl", "clip_fraction")  # the order of ``PPOLossResult.stats``
+STATS_KL = STATS + ("action_kl",)  # ... of ``ppo_loss_kl``'s
 NUM_ACTIONS = 26
 HIDDEN = 256
 TRAIN_TILE_ROWS = 64     # SKT_TILE_ROWS of csrc/skyjo_train.h: the rows of a workgroup in the forward and the backward's row pass
@@ -38,15 +49,23 @@ TRAIN_CHUNK_ROWS = 256   # SKT_CHUNK_ROWS: the rows of one partial of the weight
 class PPOLossBuffers:
     """The outputs and the scratch of ``ppo_loss`` for up to ``rows`` rows, to pass as ``out=`` minibatch after minibatch."""
 
+    _num_stats, _scratch_bytes = 6, "skyjo_vec_ppo_loss_scratch_bytes"
+
     def __init__(self, rows, device):
         if rows < 1:
             raise ValueError("rows must be at least 1")
         L = _lib.load()
         self.rows = int(rows)
-        self.stats = torch.empty((6,), dtype=torch.float64, device=device)
+        self.stats = torch.empty((self._num_stats,), dtype=torch.float64, device=device)
         self.grad_logits = torch.empty((rows, NUM_ACTIONS), dtype=torch.float32, device=device)
         self.grad_value = torch.empty((rows,), dtype=torch.float32, device=device)
-        self.scratch = torch.empty((int(L.skyjo_vec_ppo_loss_scratch_bytes(self.rows)) // 8,), dtype=torch.float64, device=device)
+        self.scratch = torch.empty((int(getattr(L, self._scratch_bytes)(self.rows)) // 8,), dtype=torch.float64, device=device)
+
+
+class PPOLossKLBuffers(PPOLossBuffers):
+    """``PPOLossBuffers`` for ``ppo_loss_kl``: seven statistics, and the scratch of ``skyjo_vec_ppo_loss_kl_scratch_bytes``."""
+
+    _num_stats, _scratch_bytes = 7, "skyjo_vec_ppo_loss_kl_scratch_bytes"
 
 
 def _column(name, t, dtype, shape, device):
@@ -99,6 +118,80 @@ def ppo_loss(logits, value, mb, clip=0.3, vf_coef=1.0, ent_coef=0.0, vf_clip=Non
     return PPOLossResult(out.stats, grad_logits, grad_value.view(value.shape))
 
 
+@torch.no_grad()
+def ppo_loss_kl(logits, value, mb, old_logits, kl_coeff=0.2, clip=0.3, vf_coef=1.0, ent_coef=0.0, vf_clip=None, out=None):
+    """``ppo_loss`` with the KL penalty against the behaviour distribution (``skyjo_vec_ppo_loss_kl``): ``old_logits`` float32 [m, 26],
+    contiguous on the inputs' GPU and starting on a 16-byte boundary - the raw logits of the policy that played, for the rows of ``mb``
+    (the second element of what ``rollout.minibatches(behaviour=True)`` yields) - and ``kl_coeff``, finite and >= 0 (RLlib's default
+    0.2; ``float(KLCoeff)`` works).  Returns ``PPOLossResult`` with ``stats`` float64 [7] in the order of ``STATS_KL``: the loss includes
+    ``kl_coeff * action_kl``, the gradient ``kl_coeff (p - p_old) / m``; ``action_kl`` is computed also when ``kl_coeff`` is 0, where
+    everything else carries the bits of ``ppo_loss``.  ``out``: a ``PPOLossKLBuffers``.  Everything else as for ``ppo_loss``."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[1] != NUM_ACTIONS or logits.shape[0] < 1:
+        raise ValueError("logits must be a float32 tensor of shape [m, 26], m >= 1")
+    dev, m, f = logits.device, logits.shape[0], torch.float32
+    if dev.type != "cuda":
+        raise ValueError("ppo_loss_kl runs on the GPU: logits is on " + str(dev))
+    _column("logits", logits, f, (m, NUM_ACTIONS), dev)
+    if not isinstance(value, torch.Tensor) or tuple(value.shape) not in ((m,), (m, 1)):
+        raise ValueError(f"value must have shape [{m}] or [{m}, 1]")
+    _column("value", value, f, tuple(value.shape), dev)
+    _column("old_logits", old_logits, f, (m, NUM_ACTIONS), dev)
+    _column("mb.log_mask", mb.log_mask, f, (m, NUM_ACTIONS), dev)
+    _column("mb.actions", mb.actions, torch.int64, (m,), dev)
+    for name in ("logp", "advantages", "value_targets", "values"):
+        _column("mb." + name, getattr(mb, name), f, (m,), dev)
+    clip, kl_coeff = float(clip), float(kl_coeff)
+    if not (math.isfinite(clip) and clip > 0.0):
+        raise ValueError("clip must be finite and greater than 0")
+    if not (math.isfinite(kl_coeff) and kl_coeff >= 0.0):
+        raise ValueError("kl_coeff must be finite and not negative")
+    vf_clip = 0.0 if vf_clip is None or not math.isfinite(float(vf_clip)) or float(vf_clip) <= 0.0 else float(vf_clip)
+    if out is None:
+        out = PPOLossKLBuffers(m, dev)
+    elif not isinstance(out, PPOLossKLBuffers) or out.rows < m or out.stats.device != dev:
+        raise ValueError("out must be a PPOLossKLBuffers of at least m rows on the inputs' device")
+    grad_logits, grad_value = out.grad_logits[:m], out.grad_value[:m]
+    if any(t.data_ptr() % 16 for t in (logits, mb.log_mask, old_logits)):
+        raise ValueError("logits, mb.log_mask and old_logits must start on a 16-byte boundary (a slice that starts at an odd row does not)")
+    L = _lib.load()
+    vp = lambda t: t.data_ptr()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.skyjo_vec_ppo_loss_kl(vp(logits), vp(mb.log_mask), vp(old_logits), vp(value), vp(mb.actions), vp(mb.logp),
+                                           vp(mb.advantages), vp(mb.value_targets), vp(mb.values), m, clip, float(vf_coef), float(ent_coef),
+                                           vf_clip, kl_coeff, vp(grad_logits), vp(grad_value), vp(out.stats), vp(out.scratch),
+                                           out.scratch.numel() * 8, stream))
+    return PPOLossResult(out.stats, grad_logits, grad_value.view(value.shape))
+
+
+class KLCoeff:
+    """RLlib's adaptive KL coefficient as a host float: ``update(mean_action_kl)`` - once per training iteration, with the mean
+    ``action_kl`` of the update's minibatches - multiplies ``coeff`` by 1.5 where the mean exceeds ``2 * target`` and by 0.5 where it
+    is below ``0.5 * target``; both inequalities are strict, a value on an edge leaves it alone.  Defaults: RLlib's ``kl_coeff`` 0.2
+    and ``kl_target`` 0.01.  The rule is restated from memory of RLlib 1.9's ``KLCoeffMixin.update_kl``, not checked against it.
+    ``float(k)`` is the coefficient.  A coefficient of 0 stays 0: start above it to have a penalty at all."""
+
+    def __init__(self, coeff=0.2, target=0.01):
+        coeff, target = float(coeff), float(target)
+        if not (math.isfinite(coeff) and coeff >= 0.0):
+            raise ValueError("coeff must be finite and not negative")
+        if not (math.isfinite(target) and target > 0.0):
+            raise ValueError("target must be finite and greater than 0")
+        self.coeff, self.target = coeff, target
+
+    def __float__(self):
+        return self.coeff
+
+    def update(self, mean_action_kl):
+        """Apply the rule; returns the coefficient."""
+        x = float(mean_action_kl)
+        if x > 2.0 * self.target:
+            self.coeff *= 1.5
+        elif x < 0.5 * self.target:
+            self.coeff *= 0.5
+        return self.coeff
+
+
 class PPOLoss(torch.autograd.Function):
     """``loss, stats = PPOLoss.apply(logits, value, mb, clip, vf_coef, ent_coef, vf_clip)``: ``ppo_loss`` inside autograd.  ``loss``
     is ``stats[0]`` as a float32 scalar; ``stats`` (float64 [6]) is not differentiable.  Backward hands the gradients the kernel
@@ -115,6 +208,24 @@ class PPOLoss(torch.autograd.Function):
     def backward(ctx, grad_loss, _grad_stats):
         grad_logits, grad_value = ctx.saved_tensors
         return grad_logits * grad_loss, grad_value * grad_loss, None, None, None, None, None
+
+
+class PPOLossKL(torch.autograd.Function):
+    """``loss, stats = PPOLossKL.apply(logits, value, mb, old_logits, kl_coeff, clip, vf_coef, ent_coef, vf_clip)``: ``ppo_loss_kl``
+    inside autograd, as ``PPOLoss`` is ``ppo_loss``: ``stats`` float64 [7], not differentiable; ``old_logits`` gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, value, mb, old_logits, kl_coeff=0.2, clip=0.3, vf_coef=1.0, ent_coef=0.0, vf_clip=None):
+        res = ppo_loss_kl(logits.detach(), value.detach(), mb, old_logits.detach(), kl_coeff=kl_coeff, clip=clip, vf_coef=vf_coef,
+                          ent_coef=ent_coef, vf_clip=vf_clip)
+        ctx.save_for_backward(res.grad_logits, res.grad_value)
+        ctx.mark_non_differentiable(res.stats)
+        return res.stats[0].to(torch.float32), res.stats
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_stats):
+        grad_logits, grad_value = ctx.saved_tensors
+        return grad_logits * grad_loss, grad_value * grad_loss, None, None, None, None, None, None, None
 
 
 class NativeAdam:

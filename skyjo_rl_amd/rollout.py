@@ -14,7 +14,9 @@ carry a target, the moments of their advantages, and shuffled minibatches as den
 ``learner.ppo_loss`` takes a ``Minibatch`` and the model's two outputs from there: the PPO loss head and its gradients in one kernel.
 Where every seat trains a policy of its own (``arena.collect`` fills the same buffer with per-seat ``logp`` and ``values``),
 ``select_rows`` / ``minibatches`` take ``seats``: the rows in which those seats acted, with the moments of their advantages alone
-(``skyjo_vec_rollout_select_seats``).
+(``skyjo_vec_rollout_select_seats``).  ``behaviour_logits`` adds the one column the KL penalty of RLlib's PPO loss needs and the
+rollout does not record - the behaviour policy's logits per row -, ``gather_behaviour`` / ``minibatches(behaviour=True)`` hand its rows
+to ``learner.ppo_loss_kl`` (``skyjo_vec_rollout_gather_logits``).
 """
 import ctypes as C
 import math
@@ -128,6 +130,36 @@ def compute_targets(buf, gamma=0.99, lam=1.0):
     return buf
 
 
+@torch.no_grad()
+def behaviour_logits(buf, policy_net):
+    """Fill ``buf.behaviour``, float32 [T, B, 26]: the raw (unmasked) logits of ``policy_net`` - the packed ``FusedNet`` that PLAYED the
+    rollout - on ``buf.records[:T]``, read in the buffer's own layout by the net's forward kernel (``FusedNet.__call__``,
+    ``skyjo_vec_mlp_forward_layout``): what ``learner.ppo_loss_kl`` takes the behaviour distribution from.  The rollout kernels keep
+    only ``logp`` of the chosen action; this is the same net on the same records once more, so
+    ``log_softmax(behaviour + log_mask)[action]`` is ``buf.logp`` within the two kernels' rounding.  The column is allocated on first
+    use and refilled afterwards; it costs T * B * 104 bytes.  A row-major buffer, and a tile-planar one of whole tiles, is ONE launch;
+    a tile-planar buffer with B % 64 != 0 goes one iteration at a time (T launches), each into the first B rows of its blocks - the
+    padding slots of the last tile are never rows.
+
+    Call it BEFORE the first optimiser step of the update: ``learner.NativeAdam`` re-packs the net in place, and after a step the net
+    is no longer the policy that played.  For an ``arena.collect`` buffer pass the net of the seat(s) about to be updated: the rows
+    in which another seat acted then hold that net's logits on a position it did not play - values nobody reads, since
+    ``minibatches(seats=...)`` selects the seat's own rows.  Returns ``buf``."""
+    _check_records(buf)
+    if policy_net.out_dim != 26 or policy_net.obs_dim != buf._env.obs_dim:
+        raise ValueError(f"policy_net must be a policy branch of this engine ({buf._env.obs_dim} inputs, 26 outputs), not "
+                         f"{policy_net.obs_dim} -> {policy_net.out_dim}")
+    if getattr(buf, "behaviour", None) is None:
+        buf.behaviour = torch.empty((buf.T, buf.B, 26), dtype=torch.float32, device=buf.actions.device)
+    T = buf.T
+    if not buf.planar or buf.B % 64 == 0:
+        policy_net(buf.records[:T], out=buf.behaviour, planar=buf.planar)
+    else:
+        for t in range(T):
+            policy_net(buf.records[t], out=buf.behaviour[t], planar=True)
+    return buf
+
+
 Selection = namedtuple("Selection", ["index", "count", "mean", "std"])
 Minibatch = namedtuple("Minibatch", ["observations", "log_mask", "actions", "logp", "advantages", "value_targets", "values", "seats"])
 
@@ -226,13 +258,45 @@ def gather_rows(buf, index, normalize=None, out=None):
     return out if out.actions.shape[0] == m else Minibatch(*(c[:m] for c in out))
 
 
-def minibatches(buf, size, generator=None, normalize=True, require=_lib.TGT_HAS_TARGET, selection=None, seats=None):
+@torch.no_grad()
+def gather_behaviour(buf, index, out=None):
+    """The rows ``index`` of ``buf.behaviour`` (``behaviour_logits`` must have run) as float32 [m, 26], one native call
+    (``skyjo_vec_rollout_gather_logits``): ``index`` as for ``gather_rows`` - any order, repeats allowed, a row id outside [0, T * B)
+    gives a row of zeros.  ``out``: a contiguous float32 [>= m, 26] tensor on the buffer's device to refill; its first m rows are
+    returned."""
+    col = getattr(buf, "behaviour", None)
+    if col is None:
+        raise ValueError("gather_behaviour needs the column of behaviour_logits(buf, policy_net)")
+    dev = buf.actions.device
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1 or index.device != dev:
+        raise ValueError("index must be a one-dimensional int64 tensor on the buffer's device")
+    if col.dtype != torch.float32 or tuple(col.shape) != (buf.T, buf.B, 26) or col.device != dev or not col.is_contiguous():
+        raise ValueError(f"buf.behaviour must be a contiguous float32 tensor of shape [{buf.T}, {buf.B}, 26] on {dev}")
+    index = index.contiguous()
+    m = index.numel()
+    if out is None:
+        out = torch.empty((m, 26), dtype=torch.float32, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] != 26 or out.shape[0] < m
+          or out.device != dev or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError("out must be a contiguous float32 tensor of shape [>= m, 26] on the buffer's device, starting on a 16-byte boundary")
+    if m == 0:  # (an empty index has no address to pass)
+        return out[:0]
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().skyjo_vec_rollout_gather_logits(col.data_ptr(), buf.T * buf.B, index.data_ptr(), m, out.data_ptr(),
+                                                               buf._env._stream()))
+    return out[:m]
+
+
+def minibatches(buf, size, generator=None, normalize=True, require=_lib.TGT_HAS_TARGET, selection=None, seats=None, behaviour=False):
     """One epoch over the selected rows in shuffled minibatches: ``select_rows`` (or a ``selection`` made earlier), a
     ``torch.randperm`` of it (``generator``: a generator on the buffer's device), and ``gather_rows`` per slice of ``size`` rows into
     ONE ``Minibatch`` that every step refills - use a batch before asking for the next.  The last slice may be short.
     ``normalize``: True - the selection's (mean, std), a std of 0 counting as 1; ``(mean, std)``; or None / False.  ``seats``: as for
     ``select_rows`` - the rows of these seats only, normalised with their own moments (``ValueError`` next to a ``selection``, which
-    has chosen its rows already)."""
+    has chosen its rows already).  ``behaviour``: True - every step yields ``(minibatch, old_logits)``, ``old_logits`` float32 [m, 26] the
+    same rows of ``buf.behaviour`` (``gather_behaviour``; ``behaviour_logits`` must have run), refilled in place like the minibatch."""
+    if behaviour and getattr(buf, "behaviour", None) is None:
+        raise ValueError("behaviour=True needs the column of behaviour_logits(buf, policy_net)")
     if seats is not None and selection is not None:
         raise ValueError("seats belongs to the selection: pass select_rows(buf, require, seats=...) as selection, or seats alone")
     sel = (select_rows(buf, require) if seats is None else select_rows(buf, require, seats=seats)) if selection is None else selection
@@ -242,5 +306,7 @@ def minibatches(buf, size, generator=None, normalize=True, require=_lib.TGT_HAS_
         normalize = None
     perm = sel.index[torch.randperm(sel.count, device=sel.index.device, generator=generator)]
     out = new_minibatch(buf, min(size, sel.count))
+    old = torch.empty((out.actions.shape[0], 26), dtype=torch.float32, device=sel.index.device) if behaviour else None
     for k in range(0, sel.count, size):
-        yield gather_rows(buf, perm[k:k + size], normalize=normalize, out=out)
+        mb = gather_rows(buf, perm[k:k + size], normalize=normalize, out=out)
+        yield (mb, gather_behaviour(buf, perm[k:k + size], out=old)) if behaviour else mb
