@@ -69,10 +69,10 @@ def _seats(env, seats):
     return seats if isinstance(seats, C.Array) and getattr(seats, "_type_", None) is _lib.SeatPolicy else seat_policies(env, seats)
 
 
-def _workspace(env, holder, sp):
-    """(pointer, bytes) of a workspace for ``sp``'s distinct nets, cached on ``holder``; (None, 0) when no seat has a net."""
-    distinct = len({s.net for s in sp if s.net})
-    need = int(_lib.load().skyjo_vec_arena_workspace_bytes(env._h, distinct))
+def _workspace(env, holder, sp, vn=()):
+    """(pointer, bytes) of a workspace for the distinct policy nets of ``sp`` and the distinct value nets of ``vn``, cached on ``holder``
+    (one attribute for ``play`` and ``collect``: the larger of the two serves both); (None, 0) when no seat has a net of either kind."""
+    need = int(_lib.load().skyjo_vec_arena_act_workspace_bytes(env._h, len({s.net for s in sp if s.net}), len({v for v in vn if v})))
     if need == 0:
         return None, 0
     ws = getattr(holder, "_arena_workspace", None)
@@ -83,6 +83,24 @@ def _workspace(env, holder, sp):
     return C.c_void_p(ws.data_ptr()), ws.numel()
 
 
+def _check_iteration(env, records, planar):
+    """``records`` is one iteration's records of ``env`` in the layout ``planar`` names, or ``ValueError``."""
+    want = (env.tiles * 64 if planar else env.num_envs) * env.record_bytes
+    if not records.is_contiguous() or records.numel() != want or records.dtype != env._torch().uint8:
+        raise ValueError(f"records must be one iteration's contiguous uint8 records ({want} bytes with planar={planar})")
+
+
+def _check_buffer(env, buf):
+    """``buf`` is a ``rollout.RolloutBuffer`` of ``env``'s shape in the layout the engine writes, or ``ValueError``."""
+    from . import rollout
+
+    rollout._check_records(buf)
+    if buf.planar != (env.record_layout == "tile-planar-all"):
+        raise ValueError(f"buf.planar={buf.planar}, but the engine's record layout is {env.record_layout!r}")
+    if buf.B != env.num_envs or buf.N != env.num_players:
+        raise ValueError("buf was made for another engine shape")
+
+
 def select(env, seats, records, seed=0, ticket=0, actions=None, planar=False, workspace=None):
     """One lockstep iteration's actions (``skyjo_vec_arena_select``): int32 [num_envs] for ``env.step``, the action of the seat each
     game's record expects.  ``records``: one iteration's records of ``env`` - [num_envs, record_bytes], or with ``planar`` one
@@ -90,9 +108,7 @@ def select(env, seats, records, seed=0, ticket=0, actions=None, planar=False, wo
     object to cache the logits' workspace on (default: the seat array)."""
     torch = env._torch()
     sp = _seats(env, seats)
-    want = (env.tiles * 64 if planar else env.num_envs) * env.record_bytes
-    if not records.is_contiguous() or records.numel() != want or records.dtype != torch.uint8:
-        raise ValueError(f"records must be one iteration's contiguous uint8 records ({want} bytes with planar={planar})")
+    _check_iteration(env, records, planar)
     if actions is None:
         actions = torch.empty((env.num_envs,), dtype=torch.int32, device=env._dev())
     elif actions.dtype != torch.int32 or actions.numel() != env.num_envs or not actions.is_contiguous():
@@ -111,11 +127,7 @@ def play(env, seats, buf, seed=0, first_ticket=0, first_records=None):
     The logits' workspace is cached on the buffer."""
     from . import rollout
 
-    rollout._check_records(buf)
-    if buf.planar != (env.record_layout == "tile-planar-all"):
-        raise ValueError(f"buf.planar={buf.planar}, but the engine's record layout is {env.record_layout!r}")
-    if buf.B != env.num_envs or buf.N != env.num_players:
-        raise ValueError("buf was made for another engine shape")
+    _check_buffer(env, buf)
     sp = _seats(env, seats)
     ws, nbytes = _workspace(env, buf, sp)
     rollout._first(env, buf, first_records)
@@ -153,20 +165,6 @@ def _values(env, values):
     return values if isinstance(values, C.Array) and getattr(values, "_type_", None) is C.c_void_p else value_nets(env, values)
 
 
-def _act_workspace(env, holder, sp, vn):
-    """(pointer, bytes) of a workspace for the distinct policy nets of ``sp`` and the distinct value nets of ``vn``, cached on ``holder``
-    (where ``play`` caches its own: the larger of the two serves both); (None, 0) when no seat has a net of either kind."""
-    need = int(_lib.load().skyjo_vec_arena_act_workspace_bytes(env._h, len({s.net for s in sp if s.net}), len({v for v in vn if v})))
-    if need == 0:
-        return None, 0
-    ws = getattr(holder, "_arena_workspace", None)
-    if ws is None or ws.numel() < need:
-        torch = env._torch()
-        ws = torch.empty((need,), dtype=torch.uint8, device=env._dev())
-        holder._arena_workspace = ws
-    return C.c_void_p(ws.data_ptr()), ws.numel()
-
-
 def act(env, seats, values, records, seed=0, ticket=0, actions=None, logp=None, values_out=None, planar=False, workspace=None,
         values_only=False):
     """One lockstep iteration with the learner's columns (``skyjo_vec_arena_act``): ``(actions, logp, values_out)`` - ``select``'s
@@ -177,9 +175,7 @@ def act(env, seats, values, records, seed=0, ticket=0, actions=None, logp=None, 
     bootstrap values of the records a rollout ends on."""
     torch = env._torch()
     sp, vn = _seats(env, seats), _values(env, values)
-    want = (env.tiles * 64 if planar else env.num_envs) * env.record_bytes
-    if not records.is_contiguous() or records.numel() != want or records.dtype != torch.uint8:
-        raise ValueError(f"records must be one iteration's contiguous uint8 records ({want} bytes with planar={planar})")
+    _check_iteration(env, records, planar)
 
     def column(name, t, dtype):
         if t is None:
@@ -194,7 +190,7 @@ def act(env, seats, values, records, seed=0, ticket=0, actions=None, logp=None, 
     else:
         actions, logp = column("actions", actions, torch.int32), column("logp", logp, torch.float32)
     values_out = column("values_out", values_out, torch.float32)
-    ws, nbytes = _act_workspace(env, sp if workspace is None else workspace, sp, vn)
+    ws, nbytes = _workspace(env, sp if workspace is None else workspace, sp, vn)
     vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     _lib.check(_lib.load().skyjo_vec_arena_act(env._h, sp, vn, vp(records), _lib.REC_TILE_PLANAR if planar else _lib.REC_ROW_MAJOR, int(seed),
                                                int(ticket), vp(actions), vp(logp), vp(values_out), ws, nbytes, env._stream()))
@@ -213,15 +209,11 @@ def collect(env, seats, values, buf, seed=0, first_ticket=0, first_records=None)
     the buffer."""
     from . import rollout
 
-    rollout._check_records(buf)
-    if buf.planar != (env.record_layout == "tile-planar-all"):
-        raise ValueError(f"buf.planar={buf.planar}, but the engine's record layout is {env.record_layout!r}")
-    if buf.B != env.num_envs or buf.N != env.num_players:
-        raise ValueError("buf was made for another engine shape")
+    _check_buffer(env, buf)
     if tuple(buf.values.shape) != (buf.T + 1, buf.B, 1):
         raise ValueError(f"buf.values must be [T + 1, B, 1], not {tuple(buf.values.shape)}")
     sp, vn = _seats(env, seats), _values(env, values)
-    ws, nbytes = _act_workspace(env, buf, sp, vn)
+    ws, nbytes = _workspace(env, buf, sp, vn)
     rollout._first(env, buf, first_records)
     vp = lambda t: t.data_ptr()
     b = _lib.RolloutBuffers(vp(buf.records), vp(buf.actions), vp(buf.logp), vp(buf.values), vp(buf.final_rewards), vp(buf.episode_end))

@@ -1,10 +1,10 @@
-// skyjo_arena.h - learner-unit kernels (included from skyjo_learner.hip after skyjo_batches.h: the statistics reduce with sk_wave_sum).
+// skyjo_arena.h - learner-unit kernels (included from skyjo_learner.hip).
 // The evaluation path beside the training rollout: every SEAT of a game has a policy of its own - a net that is sampled, a net that
 // is played greedily, or the uniform draw over the legal actions - and the episode-end columns of a buffer become per-seat results.
 // include/skyjo_vec.h (skyjo_vec_arena_*, skyjo_vec_episode_stats) and DESIGN.md 4 have the definitions; tests/arena_ref.py restates
 // the greedy rule and the statistics.
 //
-// (a) k_arena_select: one lane per game, 256 games per workgroup (k_sample's shape).  The lane reads its game's agent byte - with a
+// (a) k_arena<false>: one lane per game, 256 games per workgroup (k_sample's shape).  The lane reads its game's agent byte - with a
 //     sk_rec_byte call of its own, never through a pointer to a neighbouring byte: for the direct observation with four players the
 //     bytes Dp + 26 and Dp + 28 lie in different 16-byte pieces - and the seven mask words, and looks up the seat's kind and net.  The
 //     logits of net j lie as [B][26] floats in slice j of the workspace (one full-batch launch of the net per distinct net wrote them).
@@ -22,8 +22,14 @@
 //     by sk_wave_sum's xor tree, thread 0 the wavefronts in order: partial[b][1 + 3 N].  The finish kernel, ONE workgroup: thread t
 //     owns a contiguous span of blocks, then the tree, then the wavefronts in order (k_ppo_loss_finish's order).  No atomics: the same
 //     input gives the same bits on every call.  The rewards are read only where episode_end is set.
-// (c) k_arena_act (described where it stands, behind k_arena_select): (a) with the log-probability of the chosen action and the acting
-//     seat's own value estimate - the iteration of the arena rollouts a learner can train on.
+// (c) k_arena<true>: (a), and what a learner needs of the acting seat - the iteration of skyjo_vec_arena_act / _collect.  One body:
+//     every addition sits behind `if constexpr (ACT)`, and the actions are those of <false> for the same (seats, records, seed, ticket).
+//     logp[g] = (m[a] - mx) - __logf(sum) of the chosen action a under the seat's masked distribution: a sampled and a random seat (26
+//     zero logits: -log(number of legal actions)) take it from sk_draw_action itself, a greedy seat from sk_logp_at at its argmax.
+//     values_out[g] = output 0 of the acting seat's VALUE net on this record: the host ran one full-batch forward per distinct value
+//     net into slice j of `values` ([n] floats each, rounded up to 16 bytes), the lane reads its seat's slice at g - one coalesced
+//     load, nothing is staged - and a seat without a value net writes 0.0f.  actions == null: the values only (the bootstrap row of a
+//     buffer); no logits are read then.  The seats' value nets are a bit field like their policy nets: no private segment.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,86 +37,31 @@
 #include "../../include/skyjo_vec.h"
 #include "skyjo_draw.h"
 #include "skyjo_layout.h"
+#include "skyjo_learner_util.h"
 
 #define SK_ARENA_BLOCK 256  // games per workgroup: 256 x 26 floats of one net are one contiguous, 16-byte aligned stretch
+#define SK_ARENA_NO_VNET 15u
+static_assert(SKYJO_MAX_PLAYERS <= SK_ARENA_NO_VNET, "a seat's value net is a 4-bit field whose largest value means none");
 
-// a net's slice of the workspace, in floats: [B][26], rounded up to whole 16-byte pieces so that every slice starts on one
+// a net's slice of the workspace, in floats: [B][26] (a value net's: [B]), rounded up to whole 16-byte pieces so that every slice starts on one
 __host__ __device__ static inline long long sk_arena_slice(long long B) { return (B * SKYJO_NUM_ACTIONS + 3) & ~3LL; }
+__host__ __device__ static inline long long sk_arena_vslice(long long B) { return (B + 3) & ~3LL; }
 
 struct SkArenaArgs {
   const uint8_t *rec;    // one iteration's records, either layout
   const float *logits;   // [nets] slices of sk_arena_slice(n) floats; null when no seat has a net
-  int32_t *actions;      // [n]
+  int32_t *actions;      // [n]; k_arena<true>: null for the values only
   long long n;           // games
   uint64_t seed, ticket, game_id0;
   int32_t Dp, rec_bytes, planar, N, nets;
   uint32_t kinds;        // seat s: bits 2 s, 2 s + 1 = SKYJO_SEAT_*
   uint64_t seat_net;     // seat s: bits 4 s .. 4 s + 3 = its net's slice (unused for SKYJO_SEAT_RANDOM)
+  // k_arena<true> only
+  float *logp;           // [n]; null iff actions is
+  float *values_out;     // [n]
+  const float *values;   // [value nets] slices of sk_arena_vslice(n) floats; null when no seat has a value net
+  uint64_t seat_vnet;    // seat s: bits 4 s .. 4 s + 3 = its value net's slice, SK_ARENA_NO_VNET: none
 };
-
-__global__ __launch_bounds__(SK_ARENA_BLOCK) void k_arena_select(SkArenaArgs a) {
-  __shared__ float rows[SK_ARENA_BLOCK * SKYJO_NUM_ACTIONS];
-  __shared__ uint32_t wplayed[SK_ARENA_BLOCK / 64];
-  constexpr int K = SKYJO_NUM_ACTIONS;
-  const int tid = threadIdx.x;
-  const long long g0 = (long long)blockIdx.x * SK_ARENA_BLOCK;
-  const int nb = (int)(a.n - g0 < SK_ARENA_BLOCK ? a.n - g0 : SK_ARENA_BLOCK);
-  const bool live = tid < nb;
-  const long long g = g0 + tid;
-  uint32_t mw[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};  // 26 mask bytes from offset Dp (4-byte aligned: a word never straddles two 16-byte pieces)
-  int kind = SKYJO_SEAT_RANDOM, mine = -1;
-  if (live) {
-#pragma unroll
-    for (int k = 0; k < 7; k++) mw[k] = *(const uint32_t *)sk_rec_byte(a.rec, g, a.Dp + 4 * k, a.rec_bytes, a.planar);
-    int seat = (int)*sk_rec_byte(a.rec, g, a.Dp + 26, a.rec_bytes, a.planar);
-    seat = seat < a.N ? seat : 0;  // (a record the engine wrote never says otherwise)
-    kind = (int)((a.kinds >> (2 * seat)) & 3u);
-    mine = kind == SKYJO_SEAT_RANDOM ? -1 : (int)((a.seat_net >> (4 * seat)) & 15u);
-  }
-  float row[K];
-#pragma unroll
-  for (int k = 0; k < K; k++) row[k] = 0.f;
-  // which nets the workgroup's lanes play: a wavefront's by ballot, the four wavefronts' through 16 bytes of LDS
-  uint32_t played = 0u;
-  for (int j = 0; j < a.nets; j++) played |= __ballot(mine == j) != 0ull ? 1u << j : 0u;
-  if ((tid & 63) == 0) wplayed[tid >> 6] = played;
-  __syncthreads();
-  played = (wplayed[0] | wplayed[1]) | (wplayed[2] | wplayed[3]);
-  const int words = nb * K;
-  for (int j = 0; j < a.nets; j++) {
-    if (!((played >> j) & 1u)) continue;  // (the same answer in every lane of the workgroup)
-    __syncthreads();                      // (the lanes of the net before have their rows)
-    const float *src = a.logits + (long long)j * sk_arena_slice(a.n) + g0 * K;  // (16-byte aligned: the slice is, and 256 * 26 * 4 bytes are)
-    for (int w = tid * 4; w < words; w += SK_ARENA_BLOCK * 4) {
-      if (w + 4 <= words) {
-        const float4 v = *(const float4 *)(src + w);
-        rows[w] = v.x, rows[w + 1] = v.y, rows[w + 2] = v.z, rows[w + 3] = v.w;
-      } else {
-        for (int k = w; k < words; k++) rows[k] = src[k];
-      }
-    }
-    __syncthreads();
-    if (mine == j) {
-#pragma unroll
-      for (int k = 0; k < K; k++) row[k] = rows[tid * K + k];
-    }
-  }
-  if (!live) return;
-  int act;
-  if (kind == SKYJO_SEAT_GREEDY) {
-    float best = 0.f;
-    act = 0;
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-      const bool on = ((mw[k >> 2] >> ((k & 3) * 8)) & 0xffu) != 0;
-      const float m = on ? row[k] : row[k] + SK_DRAW_FLOAT_MIN;
-      if (k == 0 || m > best) best = m, act = k;
-    }
-  } else {
-    act = sk_draw_action(row, mw, 0, a.seed, a.ticket, a.game_id0 + (uint64_t)g, nullptr, nullptr);
-  }
-  a.actions[g] = act;
-}
 
 // The log-probability of action `act` under the masked distribution of `row`: sk_draw_action's m, mx and sum - masked logits, the
 // exponentials summed in blocks of four, the block totals left to right - and its closing expression, without the draw.  For the action
@@ -142,48 +93,31 @@ __device__ __forceinline__ float sk_logp_at(const float *row, const uint32_t *mw
   return (ma - mx) - __logf(sum);
 }
 
-// (c) k_arena_act: k_arena_select that also records what a learner needs of the acting seat - the arena's iteration for
-//     skyjo_vec_arena_act / _collect.  The same shape and the same staging; the actions are k_arena_select's for the same
-//     (seats, records, seed, ticket).  logp[g] = (m[a] - mx) - __logf(sum) of the chosen action a under the seat's masked distribution:
-//     a sampled and a random seat (26 zero logits: -log(number of legal actions)) take it from sk_draw_action itself, a greedy seat from
-//     sk_logp_at at its argmax.  values_out[g] = output 0 of the acting seat's VALUE net on this record: the host ran one full-batch
-//     forward per distinct value net into slice j of `values` ([n] floats each, rounded up to 16 bytes), the lane reads its seat's slice
-//     at g - one coalesced load, nothing is staged - and a seat without a value net writes 0.0f.  actions == null: the values only (the
-//     bootstrap row of a buffer); no logits are read then.  The seats' value nets are a bit field like their policy nets: no private
-//     segment.
-struct SkArenaActArgs {
-  SkArenaArgs s;
-  float *logp;           // [n]; null iff s.actions is
-  float *values_out;     // [n]
-  const float *values;   // [value nets] slices of sk_arena_vslice(n) floats; null when no seat has a value net
-  uint64_t seat_vnet;    // seat s: bits 4 s .. 4 s + 3 = its value net's slice, SK_ARENA_NO_VNET: none
-};
-#define SK_ARENA_NO_VNET 15u
-static_assert(SKYJO_MAX_PLAYERS <= SK_ARENA_NO_VNET, "a seat's value net is a 4-bit field whose largest value means none");
-
-__host__ __device__ static inline long long sk_arena_vslice(long long B) { return (B + 3) & ~3LL; }
-
-__global__ __launch_bounds__(SK_ARENA_BLOCK) void k_arena_act(SkArenaActArgs aa) {
+template <bool ACT>
+__global__ __launch_bounds__(SK_ARENA_BLOCK) void k_arena(SkArenaArgs a) {
   __shared__ float rows[SK_ARENA_BLOCK * SKYJO_NUM_ACTIONS];
   __shared__ uint32_t wplayed[SK_ARENA_BLOCK / 64];
   constexpr int K = SKYJO_NUM_ACTIONS;
-  const SkArenaArgs &a = aa.s;
   const int tid = threadIdx.x;
   const long long g0 = (long long)blockIdx.x * SK_ARENA_BLOCK;
   const int nb = (int)(a.n - g0 < SK_ARENA_BLOCK ? a.n - g0 : SK_ARENA_BLOCK);
   const bool live = tid < nb;
   const long long g = g0 + tid;
-  const bool acting = a.actions != nullptr;  // (a kernel argument: the same answer in every lane)
-  uint32_t mw[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  const bool acting = !ACT || a.actions != nullptr;  // (a kernel argument: the same answer in every lane)
+  uint32_t mw[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};  // 26 mask bytes from offset Dp (4-byte aligned: a word never straddles two 16-byte pieces)
   int kind = SKYJO_SEAT_RANDOM, mine = -1;
   if (live) {
-    int seat = (int)*sk_rec_byte(a.rec, g, a.Dp + 26, a.rec_bytes, a.planar);  // (a call of its own: never a neighbour's pointer)
-    seat = seat < a.N ? seat : 0;
-    const uint32_t vn = (uint32_t)((aa.seat_vnet >> (4 * seat)) & 15u);
-    aa.values_out[g] = vn == SK_ARENA_NO_VNET ? 0.0f : aa.values[(long long)vn * sk_arena_vslice(a.n) + g];
     if (acting) {
 #pragma unroll
       for (int k = 0; k < 7; k++) mw[k] = *(const uint32_t *)sk_rec_byte(a.rec, g, a.Dp + 4 * k, a.rec_bytes, a.planar);
+    }
+    int seat = (int)*sk_rec_byte(a.rec, g, a.Dp + 26, a.rec_bytes, a.planar);
+    seat = seat < a.N ? seat : 0;  // (a record the engine wrote never says otherwise)
+    if constexpr (ACT) {
+      const uint32_t vn = (uint32_t)((a.seat_vnet >> (4 * seat)) & 15u);
+      a.values_out[g] = vn == SK_ARENA_NO_VNET ? 0.0f : a.values[(long long)vn * sk_arena_vslice(a.n) + g];
+    }
+    if (acting) {
       kind = (int)((a.kinds >> (2 * seat)) & 3u);
       mine = kind == SKYJO_SEAT_RANDOM ? -1 : (int)((a.seat_net >> (4 * seat)) & 15u);
     }
@@ -192,6 +126,7 @@ __global__ __launch_bounds__(SK_ARENA_BLOCK) void k_arena_act(SkArenaActArgs aa)
   float row[K];
 #pragma unroll
   for (int k = 0; k < K; k++) row[k] = 0.f;
+  // which nets the workgroup's lanes play: a wavefront's by ballot, the four wavefronts' through 16 bytes of LDS
   uint32_t played = 0u;
   for (int j = 0; j < a.nets; j++) played |= __ballot(mine == j) != 0ull ? 1u << j : 0u;
   if ((tid & 63) == 0) wplayed[tid >> 6] = played;
@@ -201,7 +136,7 @@ __global__ __launch_bounds__(SK_ARENA_BLOCK) void k_arena_act(SkArenaActArgs aa)
   for (int j = 0; j < a.nets; j++) {
     if (!((played >> j) & 1u)) continue;  // (the same answer in every lane of the workgroup)
     __syncthreads();                      // (the lanes of the net before have their rows)
-    const float *src = a.logits + (long long)j * sk_arena_slice(a.n) + g0 * K;  // (16-byte aligned, as in k_arena_select)
+    const float *src = a.logits + (long long)j * sk_arena_slice(a.n) + g0 * K;  // (16-byte aligned: the slice is, and 256 * 26 * 4 bytes are)
     for (int w = tid * 4; w < words; w += SK_ARENA_BLOCK * 4) {
       if (w + 4 <= words) {
         const float4 v = *(const float4 *)(src + w);
@@ -218,7 +153,7 @@ __global__ __launch_bounds__(SK_ARENA_BLOCK) void k_arena_act(SkArenaActArgs aa)
   }
   if (!live) return;
   int act;
-  float lp;
+  [[maybe_unused]] float lp;
   if (kind == SKYJO_SEAT_GREEDY) {
     float best = 0.f;
     act = 0;
@@ -228,12 +163,12 @@ __global__ __launch_bounds__(SK_ARENA_BLOCK) void k_arena_act(SkArenaActArgs aa)
       const float m = on ? row[k] : row[k] + SK_DRAW_FLOAT_MIN;
       if (k == 0 || m > best) best = m, act = k;
     }
-    lp = sk_logp_at(row, mw, act);
+    if constexpr (ACT) lp = sk_logp_at(row, mw, act);
   } else {
-    act = sk_draw_action(row, mw, 0, a.seed, a.ticket, a.game_id0 + (uint64_t)g, &lp, nullptr);
+    act = sk_draw_action(row, mw, 0, a.seed, a.ticket, a.game_id0 + (uint64_t)g, ACT ? &lp : nullptr, nullptr);
   }
   a.actions[g] = act;
-  aa.logp[g] = lp;
+  if constexpr (ACT) a.logp[g] = lp;
 }
 
 #define SK_STAT_THREADS 256

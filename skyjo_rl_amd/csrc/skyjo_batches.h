@@ -1,4 +1,4 @@
-// skyjo_batches.h - learner kernels (included from skyjo_learner.hip; they read records through sk_rec_byte of skyjo_layout.h and are no
+// skyjo_batches.h - learner kernels (included from skyjo_learner.hip; they read records through SkRecords of skyjo_learner_util.h and are no
 // part of the environment's sources).  Learner minibatches of a rollout buffer: which rows take part (with the moments of their
 // advantages), and the rows of a minibatch as the dense float tensors a learner feeds its model - both on the buffer as it lies,
 // in either record layout.
@@ -11,7 +11,7 @@
 //     order - and no atomics: the same input gives the same bits on every call.
 // (b) k_gather_rows: a workgroup owns SK_GATHER_ROWS consecutive OUTPUT rows.  It fetches their records as 16-byte pieces into LDS
 //     (contiguous in a row-major buffer, 1 024 bytes apart in a tile-planar one: the addresses of sk_rec_byte), and streams the
-//     two float outputs as 16-byte stores over the run's flat [rows * D] and [rows * 26] stretches, reading the bytes out of the
+//     two float outputs as 16-byte stores over the run's flat [rows * D] and [rows * 26] stretches (sk_store_stretch), reading the bytes out of the
 //     LDS image - a mask or a meta byte is never reached by pointer arithmetic across a piece (for the direct observation the mask
 //     offset is no multiple of 16).  The columns are one lane per row.  A row id outside [0, T * B) reads nothing and gives an
 //     all-zero output row.  No private segment.
@@ -21,7 +21,7 @@
 
 #include <cfloat>
 
-#include "skyjo_layout.h"
+#include "skyjo_learner_util.h"
 
 #define SK_SEL_THREADS 256
 #define SK_SEL_WAVES (SK_SEL_THREADS / 64)
@@ -30,29 +30,35 @@
 #define SK_SEL_ROWS (SK_SEL_WAVES * SK_SEL_WAVE_ROWS)   // a block's: 4 096
 #define SK_SCAN_THREADS 1024
 
-// the sum of a wavefront, the same bits in every lane: x[l] + x[l ^ 32], then ^ 16, ... ^ 1
-__device__ __forceinline__ double sk_wave_sum(double x) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
+// SEATS (skyjo_vec_rollout_select_seats): a row also needs bit agent(row) of seat_mask, the agent byte read in place from the row's
+// record (SkRecords::of_row: k_gather_rows' numbers).  Unused otherwise.
+struct SkSelectSeats {
+  SkRecords rec;
+  uint32_t seat_mask;
+  int32_t off_agent;
+};
 
 // Phase 1 and 3 share the walk: wavefront w of block b owns rows  b * SK_SEL_ROWS + w * SK_SEL_WAVE_ROWS + k * 64 + lane,
 // k = 0 .. SK_SEL_ITERS - 1.  SCATTER = false: block_count[b] and (adv given) block_sum[2 b], [2 b + 1].  SCATTER = true:
-// block_count holds the exclusive offsets of the scan, and the selected row ids go to index_out.
-template <bool SCATTER>
+// block_count holds the exclusive offsets of the scan, and the selected row ids go to index_out.  The seat test is one more term of
+// `sel` and nothing else: with every seat in the mask the counts, the offsets and the sums carry the bits of SEATS = false, and
+// k_select_scan serves both.
+template <bool SCATTER, bool SEATS>
 __global__ __launch_bounds__(SK_SEL_THREADS) void k_select_pass(const uint8_t *flags, long long n, uint32_t require, const float *adv,
-                                                               long long *block_count, double *block_sum, long long *index_out) {
+                                                               long long *block_count, double *block_sum, long long *index_out,
+                                                               SkSelectSeats st) {
   __shared__ uint32_t wcnt[SK_SEL_WAVES];
   __shared__ double wsum[SK_SEL_WAVES], wsq[SK_SEL_WAVES];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const long long r0 = (long long)blockIdx.x * SK_SEL_ROWS + w * SK_SEL_WAVE_ROWS + lane;
   uint32_t f[SK_SEL_ITERS];
+  [[maybe_unused]] uint32_t seat[SK_SEL_ITERS];
   float av[SK_SEL_ITERS];
 #pragma unroll
   for (int k = 0; k < SK_SEL_ITERS; k++) {
     const long long r = r0 + k * 64;
     f[k] = r < n ? flags[r] : 0u;  // (require is never 0: a row past the end is not selected)
+    if constexpr (SEATS) seat[k] = r < n ? *st.rec.byte(st.rec.of_row(r), st.off_agent) : 0u;
     av[k] = 0.f;
     if (!SCATTER && adv && r < n) av[k] = adv[r];
   }
@@ -61,78 +67,8 @@ __global__ __launch_bounds__(SK_SEL_THREADS) void k_select_pass(const uint8_t *f
   double s = 0.0, q = 0.0;
 #pragma unroll
   for (int k = 0; k < SK_SEL_ITERS; k++) {
-    const bool sel = (f[k] & require) == require;
-    bal[k] = __ballot(sel);
-    cnt += (uint32_t)__popcll(bal[k]);
-    if (!SCATTER) {
-      const double a = sel ? (double)av[k] : 0.0;
-      s += a;
-      q += a * a;
-    }
-  }
-  if (!SCATTER && adv) s = sk_wave_sum(s), q = sk_wave_sum(q);
-  if (lane == 0) wcnt[w] = cnt, wsum[w] = s, wsq[w] = q;
-  __syncthreads();
-  if constexpr (!SCATTER) {
-    if (threadIdx.x == 0) {
-      block_count[blockIdx.x] = (long long)((wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]));
-      if (adv) {
-        block_sum[2 * (size_t)blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-        block_sum[2 * (size_t)blockIdx.x + 1] = ((wsq[0] + wsq[1]) + wsq[2]) + wsq[3];
-      }
-    }
-  } else {
-    long long off = block_count[blockIdx.x];
-    for (int i = 0; i < w; i++) off += wcnt[i];
-    const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int k = 0; k < SK_SEL_ITERS; k++) {
-      if ((bal[k] >> lane) & 1ull) index_out[off + __popcll(bal[k] & below)] = r0 + k * 64;
-      off += __popcll(bal[k]);
-    }
-  }
-}
-
-// k_select_pass restricted to a set of seats (skyjo_vec_rollout_select_seats): a row also needs bit agent(row) of seat_mask, the agent
-// byte read in place from the row's record - row r is game r % B of step r / B, record (r / B) * rec_stride + r % B (rec_stride: B
-// row-major, tiles * 64 tile-planar: k_gather_rows' numbers, so the padding slots of a partial tile are never rows).  The walk, the
-// ballots, the shape of the sums and the two outputs are k_select_pass's, statement for statement: with every seat in the mask the
-// counts, the offsets and the sums carry the same bits, and k_select_scan serves both.
-struct SkSelectSeats {
-  const uint8_t *rec;
-  long long rec_stride;
-  uint32_t seat_mask;
-  int32_t B, rec_bytes, off_agent, planar;
-};
-
-template <bool SCATTER>
-__global__ __launch_bounds__(SK_SEL_THREADS) void k_select_pass_seats(const uint8_t *flags, long long n, uint32_t require, const float *adv,
-                                                                     long long *block_count, double *block_sum, long long *index_out,
-                                                                     SkSelectSeats st) {
-  __shared__ uint32_t wcnt[SK_SEL_WAVES];
-  __shared__ double wsum[SK_SEL_WAVES], wsq[SK_SEL_WAVES];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const long long r0 = (long long)blockIdx.x * SK_SEL_ROWS + w * SK_SEL_WAVE_ROWS + lane;
-  uint32_t f[SK_SEL_ITERS], seat[SK_SEL_ITERS];
-  float av[SK_SEL_ITERS];
-#pragma unroll
-  for (int k = 0; k < SK_SEL_ITERS; k++) {
-    const long long r = r0 + k * 64;
-    f[k] = r < n ? flags[r] : 0u;  // (require is never 0: a row past the end is not selected)
-    seat[k] = 0u;
-    if (r < n) {
-      const long long t = r / st.B, q = st.planar ? t * st.rec_stride + (r - t * st.B) : r;
-      seat[k] = *sk_rec_byte(st.rec, q, st.off_agent, st.rec_bytes, st.planar);
-    }
-    av[k] = 0.f;
-    if (!SCATTER && adv && r < n) av[k] = adv[r];
-  }
-  unsigned long long bal[SK_SEL_ITERS];
-  uint32_t cnt = 0;
-  double s = 0.0, q = 0.0;
-#pragma unroll
-  for (int k = 0; k < SK_SEL_ITERS; k++) {
-    const bool sel = (f[k] & require) == require && seat[k] < 32u && ((st.seat_mask >> seat[k]) & 1u) != 0u;
+    bool sel = (f[k] & require) == require;
+    if constexpr (SEATS) sel = sel && seat[k] < 32u && ((st.seat_mask >> seat[k]) & 1u) != 0u;
     bal[k] = __ballot(sel);
     cnt += (uint32_t)__popcll(bal[k]);
     if (!SCATTER) {
@@ -213,7 +149,7 @@ __global__ __launch_bounds__(SK_SCAN_THREADS) void k_select_scan(long long *bloc
 #define SK_GATHER_LOADS ((SK_GATHER_ROWS * SK_GATHER_MAX_PIECES + SK_GATHER_THREADS - 1) / SK_GATHER_THREADS)
 
 struct SkGatherArgs {
-  const uint8_t *rec;        // [T (+ 1)] records, rec_stride records apart per step
+  SkRecords rec;             // [T (+ 1)] steps
   const long long *index;    // [m] row ids t * B + b, any order, repeats allowed
   const int32_t *actions;    // [T][B]
   const float *logp, *values, *adv, *vt;
@@ -221,8 +157,8 @@ struct SkGatherArgs {
   long long *act_out;
   float *logp_out, *adv_out, *vt_out, *val_out;
   uint8_t *seat_out;
-  long long m, n_rows, rec_stride;  // n_rows = T * B; rec_stride: B row-major, tiles * 64 tile-planar
-  int32_t B, vstride, rec_bytes, D, Dp, planar;
+  long long m, n_rows;       // n_rows = T * B
+  int32_t vstride, D, Dp;
   float mean, std;
 };
 
@@ -238,7 +174,7 @@ __global__ __launch_bounds__(SK_GATHER_THREADS) void k_gather_rows(SkGatherArgs 
       const long long x = a.index[o0 + tid];
       if (x >= 0 && x < a.n_rows) {
         r = x;
-        q = a.planar ? (x / a.B) * a.rec_stride + x % a.B : x;
+        q = a.rec.of_row(x);
       }
     }
     rid[tid] = r, rrec[tid] = q;
@@ -246,7 +182,7 @@ __global__ __launch_bounds__(SK_GATHER_THREADS) void k_gather_rows(SkGatherArgs 
   __syncthreads();
 
   // the records: piece c of row i.  Row-major: a row's pieces on consecutive lanes; tile-planar: piece c of 64 rows
-  const int P = a.rec_bytes >> 4, np = SK_GATHER_ROWS * P;
+  const int P = a.rec.rec_bytes >> 4, np = SK_GATHER_ROWS * P;
   uint4 v[SK_GATHER_LOADS];
   int slot[SK_GATHER_LOADS];
 #pragma unroll
@@ -255,12 +191,12 @@ __global__ __launch_bounds__(SK_GATHER_THREADS) void k_gather_rows(SkGatherArgs 
     v[k] = make_uint4(0u, 0u, 0u, 0u);
     slot[k] = -1;
     if (p < np) {
-      const int i = a.planar ? (p & (SK_GATHER_ROWS - 1)) : p / P;
-      const int c = a.planar ? (p >> 6) : p - i * P;
+      const int i = a.rec.planar ? (p & (SK_GATHER_ROWS - 1)) : p / P;
+      const int c = a.rec.planar ? (p >> 6) : p - i * P;
       if (i < rows) {
         slot[k] = i * P + c;
         const long long q = rrec[i];
-        if (q >= 0) v[k] = *(const uint4 *)sk_rec_byte(a.rec, q, c << 4, a.rec_bytes, a.planar);
+        if (q >= 0) v[k] = *(const uint4 *)a.rec.byte(q, c << 4);
       }
     }
   }
@@ -293,48 +229,13 @@ __global__ __launch_bounds__(SK_GATHER_THREADS) void k_gather_rows(SkGatherArgs 
   __syncthreads();
 
   const uint8_t *tb = (const uint8_t *)tile;
-  if (tid >= 3 * 64 && tid - 3 * 64 < rows) a.seat_out[o0 + tid - 3 * 64] = tb[(tid - 3 * 64) * a.rec_bytes + a.Dp + 26];  // (zero for a row out of range)
-  {  // observations: (float)(int8) of bytes 0 .. D - 1
-    const int total = rows * a.D;
-    float *dst = a.obs_out + o0 * a.D;
-    for (int e = tid * 4; e < total; e += SK_GATHER_THREADS * 4) {
-      int i = e / a.D, k = e - i * a.D;
-      float x[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        x[j] = e + j < total ? (float)(int8_t)tb[i * a.rec_bytes + k] : 0.f;
-        if (++k == a.D) k = 0, i++;
-      }
-      if (e + 4 <= total) {
-        *(float4 *)(dst + e) = make_float4(x[0], x[1], x[2], x[3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-          if (e + j < total) dst[e + j] = x[j];
-      }
-    }
-  }
-  {  // log of the action mask, clamped: 0 where the action is legal, -FLT_MAX where it is not
-    const int total = rows * SKYJO_NUM_ACTIONS;
-    float *dst = a.lm_out + o0 * SKYJO_NUM_ACTIONS;
-    for (int e = tid * 4; e < total; e += SK_GATHER_THREADS * 4) {
-      int i = e / SKYJO_NUM_ACTIONS, k = e - i * SKYJO_NUM_ACTIONS;
-      float x[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        x[j] = 0.f;
-        if (e + j < total && rid[i] >= 0) x[j] = tb[i * a.rec_bytes + a.Dp + k] != 0 ? 0.f : -FLT_MAX;
-        if (++k == SKYJO_NUM_ACTIONS) k = 0, i++;
-      }
-      if (e + 4 <= total) {
-        *(float4 *)(dst + e) = make_float4(x[0], x[1], x[2], x[3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-          if (e + j < total) dst[e + j] = x[j];
-      }
-    }
-  }
+  if (tid >= 3 * 64 && tid - 3 * 64 < rows) a.seat_out[o0 + tid - 3 * 64] = tb[(tid - 3 * 64) * a.rec.rec_bytes + a.Dp + 26];  // (zero for a row out of range)
+  // observations: (float)(int8) of bytes 0 .. D - 1
+  sk_store_stretch<SK_GATHER_THREADS>(a.obs_out + o0 * a.D, rows * a.D, a.D, [&](int i, int k) { return (float)(int8_t)tb[i * a.rec.rec_bytes + k]; });
+  // log of the action mask, clamped: 0 where the action is legal, -FLT_MAX where it is not
+  sk_store_stretch<SK_GATHER_THREADS>(a.lm_out + o0 * SKYJO_NUM_ACTIONS, rows * SKYJO_NUM_ACTIONS, SKYJO_NUM_ACTIONS, [&](int i, int k) {
+    return rid[i] >= 0 && tb[i * a.rec.rec_bytes + a.Dp + k] == 0 ? -FLT_MAX : 0.f;
+  });
 }
 
 // (c) k_gather_logits (skyjo_vec_rollout_gather_logits): rows of a float [n_rows][26] column - the behaviour logits a learner keeps
@@ -357,23 +258,7 @@ __global__ __launch_bounds__(SK_GATHER_THREADS) void k_gather_logits(const float
     rid[tid] = r;
   }
   __syncthreads();
-  const int total = rows * SKYJO_NUM_ACTIONS;
-  float *dst = out + o0 * SKYJO_NUM_ACTIONS;
-  for (int e = tid * 4; e < total; e += SK_GATHER_THREADS * 4) {
-    int i = e / SKYJO_NUM_ACTIONS, k = e - i * SKYJO_NUM_ACTIONS;
-    float x[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      x[j] = 0.f;
-      if (e + j < total && rid[i] >= 0) x[j] = column[rid[i] * SKYJO_NUM_ACTIONS + k];
-      if (++k == SKYJO_NUM_ACTIONS) k = 0, i++;
-    }
-    if (e + 4 <= total) {
-      *(float4 *)(dst + e) = make_float4(x[0], x[1], x[2], x[3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (e + j < total) dst[e + j] = x[j];
-    }
-  }
+  sk_store_stretch<SK_GATHER_THREADS>(out + o0 * SKYJO_NUM_ACTIONS, rows * SKYJO_NUM_ACTIONS, SKYJO_NUM_ACTIONS, [&](int i, int k) {
+    return rid[i] >= 0 ? column[rid[i] * SKYJO_NUM_ACTIONS + k] : 0.f;
+  });
 }

@@ -1,6 +1,6 @@
 // skyjo_learner.hip - the packed nets' handles and the learner behind the extern "C" boundary of include/skyjo_vec.h: skyjo_vec_mlp_*,
 // skyjo_vec_rollout_targets / _select / _gather / _gather_logits, skyjo_vec_ppo_loss / _kl, skyjo_vec_mlp_train_*, skyjo_vec_arena_* and skyjo_vec_episode_stats,
-// with their kernels (skyjo_update.h, skyjo_targets.h, skyjo_batches.h, skyjo_loss.h, skyjo_train.h, skyjo_arena.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
+// with their kernels (skyjo_update.h, skyjo_targets.h, skyjo_batches.h, skyjo_loss.h, skyjo_train.h, skyjo_arena.h; what they share: skyjo_learner_util.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
 // (skyjo_capi.hip, skyjo_device.h and its parts), and of an engine it sees what skyjo_host.h shows - the record layout, B, G, game_id0,
 // the device and the select scratch.  gfx950 only, no CPU path.
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 #include <string>
 
 #include "skyjo_host.h"
+#include "skyjo_learner_util.h"
 #include "skyjo_update.h"
 #include "skyjo_targets.h"
 #include "skyjo_batches.h"
@@ -219,11 +220,9 @@ int skyjo_vec_rollout_targets(skyjo_vec *h, const void *records, int32_t layout,
   DevGuard guard_(e.device_id);
   const SkLayout &L = *e.L;
   SkTargetsArgs a{};
-  a.rec = (const uint8_t *)records, a.values = values, a.rewards = final_rewards, a.end = episode_end;
+  a.rec = sk_records(e, records, layout), a.values = values, a.rewards = final_rewards, a.end = episode_end;
   a.adv = advantages_out, a.vt = value_targets_out, a.ret = returns_out, a.flags = flags_out;
-  a.planar = layout == SKYJO_REC_TILE_PLANAR;
-  a.rec_stride = a.planar ? (long long)e.G : (long long)e.B;
-  a.B = e.B, a.T = T, a.N = L.N, a.vstride = value_stride, a.rec_bytes = L.rec_bytes;
+  a.T = T, a.N = L.N, a.vstride = value_stride;
   a.off_agent = L.Dp + 26, a.off_done = L.Dp + 28;
   a.gamma = gamma, a.gl = gamma * lambda;  // (float32 product, rounded once: part of the definition)
   const dim3 grid((e.B + SK_TGT_LANES - 1) / SK_TGT_LANES), block(SK_TGT_LANES);
@@ -238,6 +237,29 @@ int skyjo_vec_rollout_targets(skyjo_vec *h, const void *records, int32_t layout,
 }
 
 // ---- learner minibatches of a rollout buffer (include/skyjo_vec.h: skyjo_vec_rollout_select / _gather; the kernels: skyjo_batches.h) ----
+// both entries, after their checks: the scratch, then the count pass, k_select_scan and the scatter pass.  st: the seats form's records
+// and mask, or null.  n_rows == 0 launches the scan alone, which writes the zeros.
+static int select_rows(skyjo_vec *h, const SkSelectSeats *st, const uint8_t *flags, int64_t n_rows, int32_t require_bits, const float *advantages,
+                       int64_t *index_out, int64_t *count_out, double *moments_out, hipStream_t s) {
+  const size_t nb = (size_t)((n_rows + SK_SEL_ROWS - 1) / SK_SEL_ROWS);
+  void *scratch = nullptr;
+  size_t cap = 0;
+  if (int rc = sk_engine_select_scratch(h, nb, &scratch, &cap)) return rc;
+  long long *counts = (long long *)scratch;
+  double *sums = (double *)(counts + cap);
+  const SkSelectSeats seats = st ? *st : SkSelectSeats{};
+  const dim3 grid((unsigned)nb), block(SK_SEL_THREADS);
+  const auto count = st ? k_select_pass<false, true> : k_select_pass<false, false>;
+  const auto scatter = st ? k_select_pass<true, true> : k_select_pass<true, false>;
+  if (nb) hipLaunchKernelGGL(count, grid, block, 0, s, flags, (long long)n_rows, (uint32_t)require_bits, advantages, counts, sums, (long long *)nullptr, seats);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(SK_SCAN_THREADS), 0, s, counts, (const double *)sums, (int)nb, (long long *)count_out, moments_out);
+  HIPCHK(hipGetLastError());
+  if (nb) hipLaunchKernelGGL(scatter, grid, block, 0, s, flags, (long long)n_rows, (uint32_t)require_bits, (const float *)nullptr, counts, sums, (long long *)index_out, seats);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
 int skyjo_vec_rollout_select(skyjo_vec *h, const uint8_t *flags, int64_t n_rows, int32_t require_bits, const float *advantages,
                              int64_t *index_out, int64_t *count_out, double *moments_out, void *stream) {
   if (!h || !flags || !index_out || !count_out) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_select: null argument");
@@ -245,28 +267,8 @@ int skyjo_vec_rollout_select(skyjo_vec *h, const uint8_t *flags, int64_t n_rows,
     return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_select: advantages and moments_out go together");
   if (n_rows < 0 || n_rows > (int64_t)SK_SEL_ROWS * 0x7fffffff) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_select: n_rows out of range");
   if (require_bits < 1 || require_bits > 255) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_select: require_bits must lie in 1 .. 255");
-  const SkEngineView e = sk_engine_view(h);
-  DevGuard guard_(e.device_id);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t nb = (size_t)((n_rows + SK_SEL_ROWS - 1) / SK_SEL_ROWS);
-  void *scratch = nullptr;
-  size_t cap = 0;
-  if (int rc = sk_engine_select_scratch(h, nb, &scratch, &cap)) return rc;
-  long long *counts = (long long *)scratch;
-  double *sums = (double *)(counts + cap);
-  if (nb) {
-    hipLaunchKernelGGL(k_select_pass<false>, dim3((unsigned)nb), dim3(SK_SEL_THREADS), 0, s, flags, (long long)n_rows, (uint32_t)require_bits,
-                       advantages, counts, sums, (long long *)nullptr);
-    HIPCHK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(SK_SCAN_THREADS), 0, s, counts, (const double *)sums, (int)nb, (long long *)count_out, moments_out);
-  HIPCHK(hipGetLastError());
-  if (nb) {
-    hipLaunchKernelGGL(k_select_pass<true>, dim3((unsigned)nb), dim3(SK_SEL_THREADS), 0, s, flags, (long long)n_rows, (uint32_t)require_bits,
-                       (const float *)nullptr, counts, sums, (long long *)index_out);
-    HIPCHK(hipGetLastError());
-  }
-  return SKYJO_OK;
+  DevGuard guard_(sk_engine_view(h).device_id);
+  return select_rows(h, nullptr, flags, n_rows, require_bits, advantages, index_out, count_out, moments_out, (hipStream_t)stream);
 }
 
 int skyjo_vec_rollout_select_seats(skyjo_vec *h, const void *records, int32_t layout, int32_t T, const uint8_t *flags, int32_t require_bits,
@@ -284,26 +286,9 @@ int skyjo_vec_rollout_select_seats(skyjo_vec *h, const void *records, int32_t la
   const int64_t n_rows = (int64_t)T * e.B;
   if (n_rows > (int64_t)SK_SEL_ROWS * 0x7fffffff) return fail(SKYJO_E_INVALID, std::string(who) + ": T * num_envs out of range");
   DevGuard guard_(e.device_id);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t nb = (size_t)((n_rows + SK_SEL_ROWS - 1) / SK_SEL_ROWS);
-  void *scratch = nullptr;
-  size_t cap = 0;
-  if (int rc = sk_engine_select_scratch(h, nb, &scratch, &cap)) return rc;
-  long long *counts = (long long *)scratch;
-  double *sums = (double *)(counts + cap);
   SkSelectSeats st{};
-  st.rec = (const uint8_t *)records, st.planar = layout == SKYJO_REC_TILE_PLANAR;
-  st.rec_stride = st.planar ? (long long)e.G : (long long)e.B;
-  st.seat_mask = seat_mask, st.B = e.B, st.rec_bytes = L.rec_bytes, st.off_agent = L.Dp + 26;
-  hipLaunchKernelGGL(k_select_pass_seats<false>, dim3((unsigned)nb), dim3(SK_SEL_THREADS), 0, s, flags, (long long)n_rows, (uint32_t)require_bits,
-                     advantages, counts, sums, (long long *)nullptr, st);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(SK_SCAN_THREADS), 0, s, counts, (const double *)sums, (int)nb, (long long *)count_out, moments_out);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_select_pass_seats<true>, dim3((unsigned)nb), dim3(SK_SEL_THREADS), 0, s, flags, (long long)n_rows, (uint32_t)require_bits,
-                     (const float *)nullptr, counts, sums, (long long *)index_out, st);
-  HIPCHK(hipGetLastError());
-  return SKYJO_OK;
+  st.rec = sk_records(e, records, layout), st.seat_mask = seat_mask, st.off_agent = L.Dp + 26;
+  return select_rows(h, &st, flags, n_rows, require_bits, advantages, index_out, count_out, moments_out, (hipStream_t)stream);
 }
 
 int skyjo_vec_rollout_gather(skyjo_vec *h, const void *records, int32_t layout, int32_t T, const int64_t *index, int64_t m,
@@ -326,13 +311,11 @@ int skyjo_vec_rollout_gather(skyjo_vec *h, const void *records, int32_t layout, 
   const SkLayout &L = *e.L;
   static_assert(SK_GATHER_MAX_PIECES * 16 >= ((19 + 12 * SKYJO_MAX_PLAYERS + 3) & ~3) + 32, "the largest record fits k_gather_rows' LDS image");
   SkGatherArgs a{};
-  a.rec = (const uint8_t *)records, a.index = (const long long *)index, a.actions = actions, a.logp = logp, a.values = values;
+  a.rec = sk_records(e, records, layout), a.index = (const long long *)index, a.actions = actions, a.logp = logp, a.values = values;
   a.adv = advantages, a.vt = value_targets;
   a.obs_out = obs_out, a.lm_out = logmask_out, a.act_out = (long long *)actions_out, a.logp_out = logp_out, a.adv_out = advantages_out;
   a.vt_out = value_targets_out, a.val_out = values_out, a.seat_out = seats_out;
-  a.planar = layout == SKYJO_REC_TILE_PLANAR;
-  a.m = m, a.n_rows = (long long)T * e.B, a.rec_stride = a.planar ? (long long)e.G : (long long)e.B;
-  a.B = e.B, a.vstride = value_stride, a.rec_bytes = L.rec_bytes, a.D = L.D, a.Dp = L.Dp;
+  a.m = m, a.n_rows = (long long)T * e.B, a.vstride = value_stride, a.D = L.D, a.Dp = L.Dp;
   a.mean = adv_mean, a.std = adv_std;
   hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((m + SK_GATHER_ROWS - 1) / SK_GATHER_ROWS)), dim3(SK_GATHER_THREADS), 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
@@ -503,15 +486,25 @@ namespace {
 
 struct ArenaPlan {
   SkArenaArgs a{};
-  const skyjo_vec_mlp *net[SKYJO_MAX_PLAYERS] = {};  // the distinct nets, in the order of their first seat
+  const skyjo_vec_mlp *net[SKYJO_MAX_PLAYERS] = {};   // the distinct policy nets, in the order of their first seat
+  const skyjo_vec_mlp *vnet[SKYJO_MAX_PLAYERS] = {};  // the distinct value nets, likewise
+  int vnets = 0;
+  bool act = false;  // value nets were given (skyjo_vec_arena_act / _collect): k_arena<true>
   SkEngineView e{};
 };
 
-// the seats checked against the engine, the distinct nets and the workspace; 0 or the code fail() returned
-int arena_plan(const char *who, const skyjo_vec *h, const skyjo_vec_seat_policy *seats, const void *workspace, int64_t workspace_bytes, ArenaPlan &p) {
+int64_t arena_act_bytes(int32_t B, int nets, int vnets) {
+  return ((int64_t)nets * sk_arena_slice(B) + (int64_t)vnets * sk_arena_vslice(B)) * (int64_t)sizeof(float);
+}
+
+// the seats and the value nets (null: none, the plan of skyjo_vec_arena_select / _rollout) checked against the engine, the distinct
+// nets of either kind and the workspace - the policy slices, then the value slices; 0 or the code fail() returned
+int arena_plan(const char *who, const skyjo_vec *h, const skyjo_vec_seat_policy *seats, const skyjo_vec_mlp *const *value_nets, void *workspace,
+               int64_t workspace_bytes, ArenaPlan &p) {
   const std::string name(who);
   if (!h || !seats) return fail(SKYJO_E_INVALID, name + ": null argument");
   p.e = sk_engine_view(h);
+  p.act = value_nets != nullptr;
   const SkLayout &L = *p.e.L;
   static_assert(SKYJO_MAX_PLAYERS <= 16, "a seat's net is a 4-bit field of SkArenaArgs::seat_net, its kind a 2-bit field of ::kinds");
   SkArenaArgs &a = p.a;
@@ -533,92 +526,73 @@ int arena_plan(const char *who, const skyjo_vec *h, const skyjo_vec_seat_policy 
     }
     a.kinds |= (uint32_t)kind << (2 * s);
   }
-  if (a.nets) {
+  for (int s = 0; p.act && s < L.N; s++) {
+    const skyjo_vec_mlp *m = value_nets[s];
+    int j = (int)SK_ARENA_NO_VNET;
+    if (m) {
+      if (m->net.out_dim != 1) return fail(SKYJO_E_INVALID, name + ": a seat's value net needs 1 output");
+      if (m->device_id != p.e.device_id || m->obs_dim != L.D)
+        return fail(SKYJO_E_INVALID, name + ": a seat's value net must live on the engine's device and take the engine's observation");
+      for (j = 0; j < p.vnets && p.vnet[j] != m; j++) {}
+      if (j == p.vnets) p.vnet[p.vnets++] = m;
+    }
+    a.seat_vnet |= (uint64_t)j << (4 * s);
+  }
+  if (a.nets + p.vnets) {
     if (!workspace) return fail(SKYJO_E_INVALID, name + ": seats with nets need a workspace");
     if ((uintptr_t)workspace & 15) return fail(SKYJO_E_INVALID, name + ": workspace must be 16-byte aligned");
-    if (workspace_bytes < skyjo_vec_arena_workspace_bytes(h, a.nets))
-      return fail(SKYJO_E_INVALID, name + ": workspace is smaller than skyjo_vec_arena_workspace_bytes");
+    if (workspace_bytes < arena_act_bytes(p.e.B, a.nets, p.vnets))
+      return fail(SKYJO_E_INVALID,
+                  name + ": workspace is smaller than " + (p.act ? "skyjo_vec_arena_act_workspace_bytes" : "skyjo_vec_arena_workspace_bytes"));
     a.logits = (const float *)workspace;
+    a.values = a.logits + (size_t)a.nets * sk_arena_slice(p.e.B);
   }
   a.n = p.e.B, a.game_id0 = p.e.game_id0, a.Dp = L.Dp, a.rec_bytes = L.rec_bytes, a.N = L.N;
   return SKYJO_OK;
 }
 
-// one lockstep iteration's actions: a full-batch forward per distinct net, then ONE k_arena_select
-int arena_launch(const ArenaPlan &p, const uint8_t *rec, int planar, uint64_t seed, uint64_t ticket, int32_t *actions, hipStream_t s) {
+// one lockstep iteration: a full-batch forward per distinct policy net (none when actions is null: the values only) and per distinct
+// value net, then ONE k_arena.  logp and values_out: with value nets only
+int arena_launch(const ArenaPlan &p, const uint8_t *rec, int planar, uint64_t seed, uint64_t ticket, int32_t *actions, float *logp, float *values_out,
+                 hipStream_t s) {
   SkArenaArgs a = p.a;
-  a.rec = rec, a.planar = planar, a.seed = seed, a.ticket = ticket, a.actions = actions;
+  a.rec = rec, a.planar = planar, a.seed = seed, a.ticket = ticket, a.actions = actions, a.logp = logp, a.values_out = values_out;
   const SkMlpDraw nodraw{};
-  for (int j = 0; j < a.nets; j++)
-    if (int rc = launch_mlp(p.net[j], p.net[j], 1, rec, (int)a.rec_bytes, p.net[j]->obs_dim, (int64_t)a.n,
-                            const_cast<float *>(a.logits) + (size_t)j * sk_arena_slice(a.n), nodraw, nullptr, s, planar))
-      return rc;
-  hipLaunchKernelGGL(k_arena_select, dim3((unsigned)((a.n + SK_ARENA_BLOCK - 1) / SK_ARENA_BLOCK)), dim3(SK_ARENA_BLOCK), 0, s, a);
-  HIPCHK(hipGetLastError());
-  return SKYJO_OK;
-}
-
-// ---- the arena iteration that records learner columns (skyjo_vec_arena_act / _collect; the kernel: k_arena_act) ----
-struct ArenaActPlan {
-  ArenaPlan p;
-  const skyjo_vec_mlp *vnet[SKYJO_MAX_PLAYERS] = {};  // the distinct value nets, in the order of their first seat
-  int vnets = 0;
-  uint64_t seat_vnet = 0;
-  float *values = nullptr;  // the value slices: behind the policy slices of the workspace
-};
-
-int64_t arena_act_bytes(int32_t B, int nets, int vnets) {
-  return ((int64_t)nets * sk_arena_slice(B) + (int64_t)vnets * sk_arena_vslice(B)) * (int64_t)sizeof(float);
-}
-
-// arena_plan's checks, the value nets and the larger workspace; 0 or the code fail() returned
-int arena_act_plan(const char *who, const skyjo_vec *h, const skyjo_vec_seat_policy *seats, const skyjo_vec_mlp *const *value_nets, void *workspace,
-                   int64_t workspace_bytes, ArenaActPlan &q) {
-  const std::string name(who);
-  if (!h || !seats || !value_nets) return fail(SKYJO_E_INVALID, name + ": null argument");
-  if (int rc = arena_plan(who, h, seats, workspace, workspace_bytes, q.p)) return rc;
-  const SkLayout &L = *q.p.e.L;
-  for (int s = 0; s < L.N; s++) {
-    const skyjo_vec_mlp *m = value_nets[s];
-    int j = (int)SK_ARENA_NO_VNET;
-    if (m) {
-      if (m->net.out_dim != 1) return fail(SKYJO_E_INVALID, name + ": a seat's value net needs 1 output");
-      if (m->device_id != q.p.e.device_id || m->obs_dim != L.D)
-        return fail(SKYJO_E_INVALID, name + ": a seat's value net must live on the engine's device and take the engine's observation");
-      for (j = 0; j < q.vnets && q.vnet[j] != m; j++) {}
-      if (j == q.vnets) q.vnet[q.vnets++] = m;
-    }
-    q.seat_vnet |= (uint64_t)j << (4 * s);
-  }
-  if (q.p.a.nets + q.vnets) {
-    if (!workspace) return fail(SKYJO_E_INVALID, name + ": seats with nets need a workspace");
-    if ((uintptr_t)workspace & 15) return fail(SKYJO_E_INVALID, name + ": workspace must be 16-byte aligned");
-    if (workspace_bytes < arena_act_bytes(q.p.e.B, q.p.a.nets, q.vnets))
-      return fail(SKYJO_E_INVALID, name + ": workspace is smaller than skyjo_vec_arena_act_workspace_bytes");
-    q.values = (float *)workspace + (size_t)q.p.a.nets * sk_arena_slice(q.p.e.B);
-  }
-  return SKYJO_OK;
-}
-
-// one lockstep iteration: a full-batch forward per distinct policy net (none when actions is null) and per distinct value net, then ONE k_arena_act
-int arena_act_launch(const ArenaActPlan &q, const uint8_t *rec, int planar, uint64_t seed, uint64_t ticket, int32_t *actions, float *logp,
-                     float *values_out, hipStream_t s) {
-  SkArenaActArgs aa{};
-  aa.s = q.p.a;
-  SkArenaArgs &a = aa.s;
-  a.rec = rec, a.planar = planar, a.seed = seed, a.ticket = ticket, a.actions = actions;
-  aa.logp = logp, aa.values_out = values_out, aa.values = q.values, aa.seat_vnet = q.seat_vnet;
-  const SkMlpDraw nodraw{};
+  auto forward = [&](const skyjo_vec_mlp *m, const float *out) {
+    return launch_mlp(m, m, 1, rec, (int)a.rec_bytes, m->obs_dim, (int64_t)a.n, const_cast<float *>(out), nodraw, nullptr, s, planar);
+  };
   for (int j = 0; actions && j < a.nets; j++)
-    if (int rc = launch_mlp(q.p.net[j], q.p.net[j], 1, rec, (int)a.rec_bytes, q.p.net[j]->obs_dim, (int64_t)a.n,
-                            const_cast<float *>(a.logits) + (size_t)j * sk_arena_slice(a.n), nodraw, nullptr, s, planar))
-      return rc;
-  for (int j = 0; j < q.vnets; j++)
-    if (int rc = launch_mlp(q.vnet[j], q.vnet[j], 1, rec, (int)a.rec_bytes, q.vnet[j]->obs_dim, (int64_t)a.n,
-                            q.values + (size_t)j * sk_arena_vslice(a.n), nodraw, nullptr, s, planar))
-      return rc;
-  hipLaunchKernelGGL(k_arena_act, dim3((unsigned)((a.n + SK_ARENA_BLOCK - 1) / SK_ARENA_BLOCK)), dim3(SK_ARENA_BLOCK), 0, s, aa);
+    if (int rc = forward(p.net[j], a.logits + (size_t)j * sk_arena_slice(a.n))) return rc;
+  for (int j = 0; j < p.vnets; j++)
+    if (int rc = forward(p.vnet[j], a.values + (size_t)j * sk_arena_vslice(a.n))) return rc;
+  const dim3 grid((unsigned)((a.n + SK_ARENA_BLOCK - 1) / SK_ARENA_BLOCK)), block(SK_ARENA_BLOCK);
+  if (p.act) hipLaunchKernelGGL(k_arena<true>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(k_arena<false>, grid, block, 0, s, a);
   HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+// T iterations, each arena_launch on records[t] and skyjo_vec_step_collect into records[t + 1]; with value nets logp and values are
+// recorded too and one more launch, the values only, reads the records the rollout ends on
+int arena_iterate(skyjo_vec *h, const ArenaPlan &p, int32_t T, uint64_t seed, uint64_t first_ticket, const skyjo_vec_rollout_buffers *b, void *stream) {
+  int64_t lay = 0;  // what skyjo_vec_step_collect writes: tile-planar records with SKYJO_REC_TILE_PLANAR_ALL, row-major otherwise
+  if (int rc = skyjo_vec_get_option(h, SKYJO_OPT_RECORD_LAYOUT, &lay)) return rc;
+  const int planar = lay == SKYJO_REC_TILE_PLANAR_ALL;
+  const size_t B = (size_t)p.e.B, N = (size_t)p.e.L->N, per_it = (planar ? p.e.G : B) * (size_t)p.e.L->rec_bytes;
+  uint8_t *rec = (uint8_t *)b->records;
+  for (int t = 0; t < T + (p.act ? 1 : 0); t++) {
+    const bool acting = t < T;
+    int32_t *act = acting ? b->actions + (size_t)t * B : nullptr;
+    {
+      DevGuard guard_(p.e.device_id);
+      if (int rc = arena_launch(p, rec + (size_t)t * per_it, planar, seed, first_ticket + (uint64_t)t, act, p.act && acting ? b->logp + (size_t)t * B : nullptr,
+                                p.act ? b->values + (size_t)t * B : nullptr, (hipStream_t)stream))
+        return rc;
+    }
+    if (acting)
+      if (int rc = skyjo_vec_step_collect(h, act, rec + (size_t)(t + 1) * per_it, b->final_rewards + (size_t)t * B * N, b->episode_end + (size_t)t * B, stream))
+        return rc;
+  }
   return SKYJO_OK;
 }
 
@@ -628,7 +602,13 @@ constexpr int64_t kStatMaxRows = (int64_t)SK_STAT_ROWS << 30;
 
 int64_t skyjo_vec_arena_workspace_bytes(const skyjo_vec *h, int32_t distinct_nets) {
   if (!h || distinct_nets < 0 || distinct_nets > SKYJO_MAX_PLAYERS) return 0;
-  return (int64_t)distinct_nets * sk_arena_slice(sk_engine_view(h).B) * (int64_t)sizeof(float);
+  return arena_act_bytes(sk_engine_view(h).B, distinct_nets, 0);
+}
+
+int64_t skyjo_vec_arena_act_workspace_bytes(const skyjo_vec *h, int32_t distinct_policy_nets, int32_t distinct_value_nets) {
+  if (!h || distinct_policy_nets < 0 || distinct_policy_nets > SKYJO_MAX_PLAYERS || distinct_value_nets < 0 || distinct_value_nets > SKYJO_MAX_PLAYERS)
+    return 0;
+  return arena_act_bytes(sk_engine_view(h).B, distinct_policy_nets, distinct_value_nets);
 }
 
 int skyjo_vec_arena_select(skyjo_vec *h, const skyjo_vec_seat_policy *seats, const void *records, int32_t layout, uint64_t seed, uint64_t ticket,
@@ -637,9 +617,9 @@ int skyjo_vec_arena_select(skyjo_vec *h, const skyjo_vec_seat_policy *seats, con
   if (!records || !actions_out) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
   if (int rc = check_layout(layout)) return rc;
   ArenaPlan p;
-  if (int rc = arena_plan(who, h, seats, workspace, workspace_bytes, p)) return rc;
+  if (int rc = arena_plan(who, h, seats, nullptr, workspace, workspace_bytes, p)) return rc;
   DevGuard guard_(p.e.device_id);
-  return arena_launch(p, (const uint8_t *)records, (int)(layout == SKYJO_REC_TILE_PLANAR), seed, ticket, actions_out, (hipStream_t)stream);
+  return arena_launch(p, (const uint8_t *)records, (int)(layout == SKYJO_REC_TILE_PLANAR), seed, ticket, actions_out, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int skyjo_vec_arena_rollout(skyjo_vec *h, const skyjo_vec_seat_policy *seats, int32_t T, uint64_t seed, uint64_t first_ticket,
@@ -649,42 +629,22 @@ int skyjo_vec_arena_rollout(skyjo_vec *h, const skyjo_vec_seat_policy *seats, in
   if (b->logp || b->values) return fail(SKYJO_E_INVALID, std::string(who) + ": logp and values must be NULL (the arena writes neither)");
   if (T < 1) return fail(SKYJO_E_INVALID, std::string(who) + ": T must be at least 1");
   ArenaPlan p;
-  if (int rc = arena_plan(who, h, seats, workspace, workspace_bytes, p)) return rc;
-  int64_t lay = 0;  // what skyjo_vec_step_collect writes: tile-planar records with SKYJO_REC_TILE_PLANAR_ALL, row-major otherwise
-  if (int rc = skyjo_vec_get_option(h, SKYJO_OPT_RECORD_LAYOUT, &lay)) return rc;
-  const int planar = lay == SKYJO_REC_TILE_PLANAR_ALL;
-  const size_t B = (size_t)p.e.B, N = (size_t)p.e.L->N, per_it = (planar ? p.e.G : B) * (size_t)p.e.L->rec_bytes;
-  uint8_t *rec = (uint8_t *)b->records;
-  for (int t = 0; t < T; t++) {
-    int32_t *act = b->actions + (size_t)t * B;
-    {
-      DevGuard guard_(p.e.device_id);
-      if (int rc = arena_launch(p, rec + (size_t)t * per_it, planar, seed, first_ticket + (uint64_t)t, act, (hipStream_t)stream)) return rc;
-    }
-    if (int rc = skyjo_vec_step_collect(h, act, rec + (size_t)(t + 1) * per_it, b->final_rewards + (size_t)t * B * N, b->episode_end + (size_t)t * B, stream))
-      return rc;
-  }
-  return SKYJO_OK;
-}
-
-int64_t skyjo_vec_arena_act_workspace_bytes(const skyjo_vec *h, int32_t distinct_policy_nets, int32_t distinct_value_nets) {
-  if (!h || distinct_policy_nets < 0 || distinct_policy_nets > SKYJO_MAX_PLAYERS || distinct_value_nets < 0 || distinct_value_nets > SKYJO_MAX_PLAYERS)
-    return 0;
-  return arena_act_bytes(sk_engine_view(h).B, distinct_policy_nets, distinct_value_nets);
+  if (int rc = arena_plan(who, h, seats, nullptr, workspace, workspace_bytes, p)) return rc;
+  return arena_iterate(h, p, T, seed, first_ticket, b, stream);
 }
 
 int skyjo_vec_arena_act(skyjo_vec *h, const skyjo_vec_seat_policy *seats, const skyjo_vec_mlp *const *value_nets, const void *records, int32_t layout,
                         uint64_t seed, uint64_t ticket, int32_t *actions_out, float *logp_out, float *values_out, void *workspace,
                         int64_t workspace_bytes, void *stream) {
   static const char *who = "skyjo_vec_arena_act";
-  if (!records || !values_out) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
+  if (!records || !values_out || !value_nets) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
   if ((actions_out == nullptr) != (logp_out == nullptr)) return fail(SKYJO_E_INVALID, std::string(who) + ": actions_out and logp_out go together");
   if (int rc = check_layout(layout)) return rc;
-  ArenaActPlan q;
-  if (int rc = arena_act_plan(who, h, seats, value_nets, workspace, workspace_bytes, q)) return rc;
-  DevGuard guard_(q.p.e.device_id);
-  return arena_act_launch(q, (const uint8_t *)records, (int)(layout == SKYJO_REC_TILE_PLANAR), seed, ticket, actions_out, logp_out, values_out,
-                          (hipStream_t)stream);
+  ArenaPlan p;
+  if (int rc = arena_plan(who, h, seats, value_nets, workspace, workspace_bytes, p)) return rc;
+  DevGuard guard_(p.e.device_id);
+  return arena_launch(p, (const uint8_t *)records, (int)(layout == SKYJO_REC_TILE_PLANAR), seed, ticket, actions_out, logp_out, values_out,
+                      (hipStream_t)stream);
 }
 
 int skyjo_vec_arena_collect(skyjo_vec *h, const skyjo_vec_seat_policy *seats, const skyjo_vec_mlp *const *value_nets, int32_t T, uint64_t seed,
@@ -693,27 +653,10 @@ int skyjo_vec_arena_collect(skyjo_vec *h, const skyjo_vec_seat_policy *seats, co
   if (!b || !b->records || !b->actions || !b->logp || !b->values || !b->final_rewards || !b->episode_end)
     return fail(SKYJO_E_INVALID, std::string(who) + ": null argument (every column of the buffers is required)");
   if (T < 1) return fail(SKYJO_E_INVALID, std::string(who) + ": T must be at least 1");
-  ArenaActPlan q;
-  if (int rc = arena_act_plan(who, h, seats, value_nets, workspace, workspace_bytes, q)) return rc;
-  int64_t lay = 0;  // what skyjo_vec_step_collect writes: as skyjo_vec_arena_rollout decides it
-  if (int rc = skyjo_vec_get_option(h, SKYJO_OPT_RECORD_LAYOUT, &lay)) return rc;
-  const int planar = lay == SKYJO_REC_TILE_PLANAR_ALL;
-  const SkEngineView &e = q.p.e;
-  const size_t B = (size_t)e.B, N = (size_t)e.L->N, per_it = (planar ? e.G : B) * (size_t)e.L->rec_bytes;
-  uint8_t *rec = (uint8_t *)b->records;
-  for (int t = 0; t <= T; t++) {  // t == T: the values-only pass on the records the rollout ends on
-    int32_t *act = t < T ? b->actions + (size_t)t * B : nullptr;
-    {
-      DevGuard guard_(e.device_id);
-      if (int rc = arena_act_launch(q, rec + (size_t)t * per_it, planar, seed, first_ticket + (uint64_t)t, act, t < T ? b->logp + (size_t)t * B : nullptr,
-                                    b->values + (size_t)t * B, (hipStream_t)stream))
-        return rc;
-    }
-    if (t < T)
-      if (int rc = skyjo_vec_step_collect(h, act, rec + (size_t)(t + 1) * per_it, b->final_rewards + (size_t)t * B * N, b->episode_end + (size_t)t * B, stream))
-        return rc;
-  }
-  return SKYJO_OK;
+  if (!value_nets) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
+  ArenaPlan p;
+  if (int rc = arena_plan(who, h, seats, value_nets, workspace, workspace_bytes, p)) return rc;
+  return arena_iterate(h, p, T, seed, first_ticket, b, stream);
 }
 
 int64_t skyjo_vec_episode_stats_scratch_bytes(int64_t rows, int32_t num_players) {

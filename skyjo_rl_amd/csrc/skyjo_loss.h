@@ -1,4 +1,4 @@
-// skyjo_loss.h - learner kernels (included from skyjo_learner.hip after skyjo_batches.h: they reduce with sk_wave_sum).
+// skyjo_loss.h - learner kernels (included from skyjo_learner.hip).
 // The PPO loss head of a learner minibatch: from the policy branch's raw logits, the log-mask and the value output to the loss, its
 // statistics and the gradients with respect to the logits and the value - what stands between a model's two outputs and
 // optimizer.step().  include/skyjo_vec.h (skyjo_vec_ppo_loss) and DESIGN.md 4 have the definition; tests/ppo_loss_ref.py restates it.
@@ -8,9 +8,10 @@
 //     which is read dword by dword) and keeps ONE image in LDS: z = logits + log_mask, row i at dword i * SK_LOSS_STRIDE.  The stride
 //     is 27, not 26: ds_read_b32 serves 32 lanes per cycle out of 32 banks, and 26 i mod 32 meets every bank twice.  Lane i then
 //     does row i in float32 - max-subtracted softmax, ratio, clipped surrogate, entropy, value loss - writes the 26 gradients over
-//     its z and the value gradient to its column; the image leaves as 16-byte stores over the run's flat [rows * 26] stretch, the
-//     shape of k_gather_rows' float outputs.  A row's loss terms, kl and clip bit are widened to double, a wavefront sums them by
-//     sk_wave_sum's xor tree, thread 0 adds the wavefronts in order: partial[6 b .. 6 b + 5].  No atomics, no private segment.
+//     its z and the value gradient to its column; the image leaves as 16-byte stores over the run's flat [rows * 26] stretch
+//     (sk_store_stretch: the loop of k_gather_rows' float outputs).  A row's loss terms, kl and clip bit are widened to double, a
+//     wavefront sums them by sk_wave_sum's xor tree, thread 0 adds the wavefronts in order: partial[6 b .. 6 b + 5].  No atomics, no
+//     private segment.
 // (b) k_ppo_loss_finish, ONE workgroup: thread t owns a contiguous span of blocks, then the wavefront's tree, then the wavefronts in
 //     order (k_select_scan's order), divided by m: stats[0 .. 5] = loss, policy_loss, vf_loss, entropy, kl, clip_fraction.
 //     The same input gives the same bits on every call.
@@ -25,6 +26,7 @@
 #include <stdint.h>
 
 #include "../../include/skyjo_vec.h"
+#include "skyjo_learner_util.h"
 
 #define SK_LOSS_ROWS 128     // even: a run's byte length (rows * 104) is a multiple of 16
 #define SK_LOSS_THREADS 128  // one lane per row
@@ -192,25 +194,8 @@ __global__ __launch_bounds__(SK_LOSS_THREADS) void k_ppo_loss(SkLossArgs a) {
     a.partial[(size_t)blockIdx.x * NS + tid] = s;
   }
 
-  {  // the gradients, out of the image
-    float *dst = a.g_logits + o0 * K;
-    for (int e = tid * 4; e < total; e += SK_LOSS_THREADS * 4) {
-      int i = e / K, k = e - i * K;
-      float x[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        x[j] = e + j < total ? zs[i * SK_LOSS_STRIDE + k] : 0.f;
-        if (++k == K) k = 0, i++;
-      }
-      if (e + 4 <= total) {
-        *(float4 *)(dst + e) = make_float4(x[0], x[1], x[2], x[3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-          if (e + j < total) dst[e + j] = x[j];
-      }
-    }
-  }
+  // the gradients, out of the image
+  sk_store_stretch<SK_LOSS_THREADS>(a.g_logits + o0 * K, total, K, [&](int i, int k) { return zs[i * SK_LOSS_STRIDE + k]; });
 }
 
 template <int NS>  // SK_LOSS_STATS, or SK_LOSS_KL_STATS after k_ppo_loss<true>

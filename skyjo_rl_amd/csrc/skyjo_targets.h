@@ -1,4 +1,4 @@
-// skyjo_targets.h - a learner kernel (included from skyjo_learner.hip; it reads records through sk_rec_byte of skyjo_layout.h and is no
+// skyjo_targets.h - a learner kernel (included from skyjo_learner.hip; it reads records through SkRecords of skyjo_learner_util.h and is no
 // part of the environment's sources).  Learner targets of a rollout buffer: per-seat GAE(gamma, lambda), one lane per game.
 //
 // What RLlib's PPO computes per agent trajectory for the sample batches of the reference's trainer
@@ -21,20 +21,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "skyjo_layout.h"
+#include "skyjo_learner_util.h"
 
 #define SK_TGT_BLOCK 16  // time steps whose inputs are in flight together
 #define SK_TGT_LANES 64  // one wavefront per workgroup: 65 536 games = one wavefront per SIMD
 
 struct SkTargetsArgs {
-  const uint8_t *rec;      // [T + 1] records, rec_stride records apart per step
   const float *values;     // [T + 1][B][vstride]
   const double *rewards;   // [T][B][N]
   const uint8_t *end;      // [T][B]
   float *adv, *vt, *ret;   // [T][B]
   uint8_t *flags;          // [T][B]
-  long long rec_stride;    // records per step: B row-major, tiles * 64 tile-planar
-  int32_t B, T, N, vstride, rec_bytes, off_agent, off_done, planar;
+  SkRecords rec;           // [T + 1] steps
+  int32_t T, N, vstride, off_agent, off_done;
   float gamma, gl;         // gl = float32(gamma) * float32(lambda), rounded once on the host
 };
 
@@ -69,9 +68,9 @@ __global__ __launch_bounds__(SK_TGT_LANES) void k_rollout_targets(SkTargetsArgs 
   constexpr int NR = REGS ? NS : 1;
   __shared__ float cols[REGS ? 1 : 3 * SKYJO_MAX_PLAYERS * SK_TGT_LANES];
   const int b = blockIdx.x * SK_TGT_LANES + threadIdx.x;
-  if (b >= a.B) return;  // (no barrier below: the columns are lane-private)
+  if (b >= a.rec.B) return;  // (no barrier below: the columns are lane-private)
   const int N = REGS ? NS : a.N;
-  const size_t B = (size_t)a.B;
+  const size_t B = (size_t)a.rec.B;
 
   // seat states as two bit sets: TERMINAL, NEXT, neither = UNKNOWN
   uint32_t term = 0, next = 0;
@@ -90,9 +89,9 @@ __global__ __launch_bounds__(SK_TGT_LANES) void k_rollout_targets(SkTargetsArgs 
   } while (0)
 
   {  // the bootstrap: the seat that would act on records[T] starts NEXT with values[T]
-    const long long r = (long long)a.T * a.rec_stride + b;
-    const int s = *sk_rec_byte(a.rec, r, a.off_agent, a.rec_bytes, a.planar);
-    if (*sk_rec_byte(a.rec, r, a.off_done, a.rec_bytes, a.planar) == 0 && s < N) {
+    const long long r = a.rec.at(a.T, b);
+    const int s = *a.rec.byte(r, a.off_agent);
+    if (*a.rec.byte(r, a.off_done) == 0 && s < N) {
       next = 1u << s;
       SEAT_SET(nv, s, a.values[((size_t)a.T * B + b) * a.vstride]);
       SEAT_SET(na, s, 0.f);
@@ -109,9 +108,9 @@ __global__ __launch_bounds__(SK_TGT_LANES) void k_rollout_targets(SkTargetsArgs 
       const int t = hi - 1 - k;
       seat[k] = 0, done[k] = 1, end[k] = 0, V[k] = 0.f;
       if (t >= lo) {
-        const long long r = (long long)t * a.rec_stride + b;
-        seat[k] = *sk_rec_byte(a.rec, r, a.off_agent, a.rec_bytes, a.planar);
-        done[k] = *sk_rec_byte(a.rec, r, a.off_done, a.rec_bytes, a.planar);
+        const long long r = a.rec.at(t, b);
+        seat[k] = *a.rec.byte(r, a.off_agent);
+        done[k] = *a.rec.byte(r, a.off_done);
         end[k] = a.end[(size_t)t * B + b];
         V[k] = a.values[((size_t)t * B + b) * a.vstride];
       }

@@ -1,5 +1,5 @@
 """numpy references for the kernels that read the engine's records on the caller's side - ``k_episode_ends``, ``k_unpack``, ``k_sample``
-(csrc/skyjo_callers.h), the pair draw in the net's epilogue and ``k_arena_select`` (csrc/skyjo_arena.h) - and synthetic records for
+(csrc/skyjo_callers.h), the pair draw in the net's epilogue and ``k_arena`` (csrc/skyjo_arena.h) - and synthetic records for
 them at EVERY record geometry: the indirect observation and the direct one with 1 .. 12 players (record_bytes 64 .. 208, 4 .. 13
 16-byte pieces), in both layouts.  numpy only, nothing from the package, deterministic from seeds (TEST INFRASTRUCTURE).  Written from
 include/skyjo_vec.h (the record, skyjo_vec_episode_ends, skyjo_vec_unpack, skyjo_vec_*_layout); it shares no code with the library.

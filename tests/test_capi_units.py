@@ -12,8 +12,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "skyjo_rl_amd", "csrc")
 DEVICE_PARTS = {"skyjo_device.h", "skyjo_rng.h", "skyjo_transition.h", "skyjo_record.h", "skyjo_step.h", "skyjo_deal.h", "skyjo_cycle.h",
                 "skyjo_callers.h"}
-LEARNER_HEADERS = {"skyjo_targets.h", "skyjo_batches.h", "skyjo_loss.h", "skyjo_update.h"}
-LEARNER_KERNELS = ("k_rollout_targets", "k_select_pass", "k_select_scan", "k_gather_rows", "k_ppo_loss", "k_ppo_loss_finish", "k_mlp_update")
+LEARNER_HEADERS = {"skyjo_targets.h", "skyjo_batches.h", "skyjo_loss.h", "skyjo_update.h", "skyjo_train.h", "skyjo_arena.h", "skyjo_learner_util.h"}
+LEARNER_KERNELS = ("k_rollout_targets", "k_select_pass", "k_select_scan", "k_gather_rows", "k_gather_logits", "k_ppo_loss", "k_ppo_loss_finish",
+                   "k_mlp_update", "k_mlp_train_fwd", "k_mlp_train_bwd_rows", "k_mlp_train_bwd_weights", "k_mlp_train_bwd_finish", "k_arena",
+                   "k_episode_stats", "k_episode_stats_finish")
 ENV_KERNELS = ("k_cycle", "k_step", "k_deal", "k_reset", "k_observe")
 
 

@@ -2,7 +2,7 @@
 greedy and random seats, and the per-seat results of the episodes that end.
 
 Shapes: engines with the indirect observation and auto_reset, N in {2, 3, 4}, num_envs in {1, 63, 130} - one lane, a partial tile of
-k_arena_select's 256 lanes and of the records' 64, two record tiles plus a partial one - row-major, and tile-planar-all at N = 3 x 130.
+k_arena's 256 lanes and of the records' 64, two record tiles plus a partial one - row-major, and tile-planar-all at N = 3 x 130.
 The nets are ``FusedNet(model.policy, precision="fp32")`` of seeded ``ActionMaskModel``s.  Expected actions are built from entry points
 that existed before the arena (the net's forward, ``skyjo_vec_sample_actions_layout``) and tests/arena_ref.py; every comparison of
 actions, records and flags is exact.

@@ -3,7 +3,7 @@ skyjo_vec_arena_act, skyjo_vec_arena_collect, skyjo_vec_rollout_select_seats) an
 (``rollout.select_rows`` / ``minibatches`` with ``seats``, ``examples.ppo.ppo_update_per_seat``).
 
 Shapes: those of tests/test_gpu_arena.py (N in {2, 3, 4} x num_envs in {1, 63, 130} row-major, N = 3 x 130 tile-planar-all: one lane,
-a partial workgroup of k_arena_act's 256 lanes, a partial record tile) and the synthetic records of tests/record_ref.py (321 games: a
+a partial workgroup of k_arena's 256 lanes, a partial record tile) and the synthetic records of tests/record_ref.py (321 games: a
 second, partial workgroup).  Actions, values, records and flags are compared bit for bit; ``logp`` of a seat that is not the training
 rollout's against float64 within ``net_ref.check_draw``'s bound, 1e-5 + 4 x 2^-24 |logp_ref|.
 

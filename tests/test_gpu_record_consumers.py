@@ -1,5 +1,5 @@
 """The kernels that read the engine's records on the caller's side - ``k_episode_ends``, ``k_unpack``, ``k_sample`` (csrc/skyjo_callers.h),
-the pair draw in the net's epilogue and ``k_arena_select`` - on the synthetic records of tests/record_ref.py: every record geometry (the
+the pair draw in the net's epilogue and ``k_arena`` - on the synthetic records of tests/record_ref.py: every record geometry (the
 indirect observation, the direct one with 1 .. 12 players), both layouts, every planar input with dirty padding, against the numpy
 restatements of the header's contracts.  Every comparison is bit for bit, but the draw against float64, which is
 ``net_ref.check_draw`` as tests/test_gpu_net_synthetic.py uses it.  Every output lies between guard bytes that must stay untouched
