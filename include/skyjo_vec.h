@@ -546,7 +546,8 @@ int skyjo_vec_rollout_gather_logits(const float *column /* [n_rows][26] */, int6
  *   value          float32 [m];  actions int64 [m], each in [0, 26) - a precondition: an action outside is read as action 0
  *   logp_old, advantages, value_targets, values_old  float32 [m]
  *   clip > 0 (finite);  vf_coef;  ent_coef;  vf_clip: <= 0, +inf or NaN mean "no value clipping"
- * Per row, in float32:  z = logits + log_mask;  M = max z;  e = exp(z - M);  S = sum e;  logp = z - M - log S;  p = e / S (a masked
+ * Per row, in double from the float32 inputs (every output is rounded once; the device's float32 logf carries a mean signed error of
+ * -7e-08 on 1 <= S <= 26 that does not average out over the rows' kl and entropy):  z = logits + log_mask;  M = max z;  e = exp(z - M);  S = sum e;  logp = z - M - log S;  p = e / S (a masked
  * action has p == 0 exactly);  lp = logp[action];  r = exp(lp - logp_old);  A = advantage;
  *   pl = -min(r A, clamp(r, 1 - clip, 1 + clip) A);   H = -sum over p > 0 of p logp;   kl = logp_old - lp;
  *   vl = (v - vt)^2, and with value clipping vl = max(vl, (vc - vt)^2), vc = v_old + clamp(v - v_old, -vf_clip, vf_clip);
@@ -556,7 +557,7 @@ int skyjo_vec_rollout_gather_logits(const float *column /* [n_rows][26] */, int6
  *                                   entropy term is exactly 0 where p_k == 0, so a masked k != action gets exactly 0.0; 16-byte aligned
  *   grad_value_out  float32 [m]     1/m vf_coef d, d = 2 (v - vt) - but 0 where the value clamp saturates and (vc - vt)^2 > (v - vt)^2
  *   stats_out       double [6]      loss, policy_loss, vf_loss, entropy, kl, clip_fraction: means over the m rows; every row's terms are
- *                                   widened to double first and summed in a fixed order without atomics - the same input gives the
+ *                                   doubles and summed in a fixed order without atomics - the same input gives the
  *                                   same bits on every call
  *   scratch         caller-owned, 8-byte aligned, at least skyjo_vec_ppo_loss_scratch_bytes(m) bytes (the per-workgroup partial sums)
  * These are the gradients torch's autograd gives for the same expression.  SKYJO_E_INVALID on a null pointer, m < 1, a clip that is
@@ -573,10 +574,10 @@ int skyjo_vec_ppo_loss(const float *logits, const float *log_mask, const float *
  * promises of skyjo_vec_ppo_loss, and:
  *   old_logits     float32 [m][26]  the behaviour policy's raw logits of the rows (skyjo_vec_rollout_gather_logits); 16-byte aligned
  *   kl_coeff       finite, >= 0
- * Per row, in float32, beside the above:  zo = old_logits + log_mask;  Mo = max zo;  So = sum exp(zo - Mo);  logpo = zo - Mo - log So;
+ * Per row, in double, beside the above:  zo = old_logits + log_mask;  Mo = max zo;  So = sum exp(zo - Mo);  logpo = zo - Mo - log So;
  * po = exp(zo - Mo) / So;
  *   akl = sum over k with po_k > 0 of po_k (logpo_k - logp_k)      KL(pi_old || pi_new); logp_k is finite wherever the action is legal,
- *                                                                  also where p_k underflowed to 0
+ *                                                                  also where p_k underflowed to 0 (in double: a gap of 745)
  * L = 1/m sum (pl + vf_coef vl - ent_coef H + kl_coeff akl).  The outputs:
  *   grad_logits_out   as above, plus 1/m kl_coeff (p_k - po_k) - 0 at a masked k, where p_k == po_k == 0: the masked k != action still gets
  *                     exactly 0.0.  With kl_coeff == 0 nothing is added: the bits of skyjo_vec_ppo_loss

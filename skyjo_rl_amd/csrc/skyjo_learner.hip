@@ -370,10 +370,9 @@ static int ppo_loss(const char *who, const bool KL, const float *logits, const f
   a.logits = logits, a.log_mask = log_mask, a.old_logits = old_logits, a.value = value, a.actions = (const long long *)actions;
   a.logp_old = logp_old, a.adv = advantages, a.vt = value_targets, a.v_old = values_old, a.g_logits = grad_logits_out, a.g_value = grad_value_out;
   a.partial = (double *)scratch, a.m = m;
-  a.lo = (float)(1.0 - (double)clip), a.hi = (float)(1.0 + (double)clip);
+  a.lo = 1.0 - (double)clip, a.hi = 1.0 + (double)clip;
   a.vf_coef = vf_coef, a.ent_coef = ent_coef;
   a.vf_clip = (std::isfinite(vf_clip) && vf_clip > 0.f) ? vf_clip : 0.f;
-  a.inv_m = 1.0f / (float)m;
   a.kl_coeff = kl_coeff;
   const int64_t nb = (m + SK_LOSS_ROWS - 1) / SK_LOSS_ROWS;
   hipStream_t s = (hipStream_t)stream;

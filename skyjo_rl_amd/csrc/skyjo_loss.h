@@ -7,7 +7,9 @@
 //     (the run starts on a 16-byte boundary and, SK_LOSS_ROWS being even, is a whole number of pieces but for the last run's tail,
 //     which is read dword by dword) and keeps ONE image in LDS: z = logits + log_mask, row i at dword i * SK_LOSS_STRIDE.  The stride
 //     is 27, not 26: ds_read_b32 serves 32 lanes per cycle out of 32 banks, and 26 i mod 32 meets every bank twice.  Lane i then
-//     does row i in float32 - max-subtracted softmax, ratio, clipped surrogate, entropy, value loss - writes the 26 gradients over
+//     does row i in DOUBLE from the float32 image - max-subtracted softmax, ratio, clipped surrogate, entropy, value loss; the
+//     device's float32 logf has a mean signed error of -7e-08 on 1 <= S <= 26, which does not average out over rows and sat whole in
+//     the kl and entropy statistics (EXPERIMENTS); 26 elements a row make the wider arithmetic free - rounds each of the 26 gradients once over
 //     its z and the value gradient to its column; the image leaves as 16-byte stores over the run's flat [rows * 26] stretch
 //     (sk_store_stretch: the loop of k_gather_rows' float outputs).  A row's loss terms, kl and clip bit are widened to double, a
 //     wavefront sums them by sk_wave_sum's xor tree, thread 0 adds the wavefronts in order: partial[6 b .. 6 b + 5].  No atomics, no
@@ -46,9 +48,8 @@ struct SkLossArgs {
   float *g_value;                  // [m]
   double *partial;                 // [blocks][6], <true>: [blocks][7]
   long long m;
-  float lo, hi;                    // 1 - clip, 1 + clip (rounded once from double)
+  double lo, hi;                   // 1 - clip, 1 + clip, in double from the float32 clip
   float vf_coef, ent_coef, vf_clip;  // vf_clip <= 0: no value clipping
-  float inv_m;
   float kl_coeff;                  // >= 0 (k_ppo_loss<true> only)
 };
 
@@ -105,79 +106,81 @@ __global__ __launch_bounds__(SK_LOSS_THREADS) void k_ppo_loss(SkLossArgs a) {
     float *zr = zs + tid * SK_LOSS_STRIDE;
     const long long act = a.actions[o];
     const int ai = (unsigned long long)act < (unsigned long long)K ? (int)act : 0;  // (the precondition; never out of the image)
-    const float lp_old = a.logp_old[o], A = a.adv[o], v = a.value[o], vt = a.vt[o], vo = a.v_old[o];
-    float z[K];
+    // every float32 input of the row is widened once; the row is evaluated in double and every output rounded once (header)
+    const double lp_old = a.logp_old[o], A = a.adv[o], v = a.value[o], vt = a.vt[o], vo = a.v_old[o];
+    const double inv_m = 1.0 / (double)a.m, lo = a.lo, hi = a.hi;  // (1 / m is rounded once, in double)
+    double z[K];
 #pragma unroll
-    for (int k = 0; k < K; k++) z[k] = zr[k];
-    float M = z[0];
+    for (int k = 0; k < K; k++) z[k] = (double)zr[k];
+    double M = z[0];
 #pragma unroll
-    for (int k = 1; k < K; k++) M = fmaxf(M, z[k]);
-    float p[K], S = 0.f;
+    for (int k = 1; k < K; k++) M = fmax(M, z[k]);
+    double p[K], S = 0.0;
 #pragma unroll
     for (int k = 0; k < K; k++) {
       z[k] -= M;
-      p[k] = expf(z[k]);
+      p[k] = exp(z[k]);
       S += p[k];
     }
-    const float logS = logf(S);
-    float H = 0.f;
+    const double logS = log(S);
+    double H = 0.0;
 #pragma unroll
     for (int k = 0; k < K; k++) {
       p[k] /= S;
       z[k] -= logS;  // logp_k
-      if (p[k] > 0.f) H -= p[k] * z[k];
+      if (p[k] > 0.0) H -= p[k] * z[k];
     }
-    const float lp = (zr[ai] - M) - logS;
-    const float r = expf(lp - lp_old);
-    const float pl = -fminf(r * A, fminf(fmaxf(r, a.lo), a.hi) * A);
-    const bool clipped = (A > 0.f && r > a.hi) || (A < 0.f && r < a.lo);
+    const double lp = ((double)zr[ai] - M) - logS;
+    const double r = exp(lp - lp_old);
+    const double pl = -fmin(r * A, fmin(fmax(r, lo), hi) * A);
+    const bool clipped = (A > 0.0 && r > hi) || (A < 0.0 && r < lo);
     // -g r (delta_ka - p_k) with 1 - p_a taken as the sum of the others: a chosen action whose p rounds to 1 keeps its gradient,
     // and the 26 terms of a row sum to 0 within their roundings
-    const float gs = a.inv_m * (clipped ? 0.f : A * r), es = a.inv_m * a.ent_coef;
-    float q = 0.f;
+    const double gs = inv_m * (clipped ? 0.0 : A * r), es = inv_m * (double)a.ent_coef;
+    double q = 0.0;
 #pragma unroll
-    for (int k = 0; k < K; k++) q += k == ai ? 0.f : p[k];
+    for (int k = 0; k < K; k++) q += k == ai ? 0.0 : p[k];
     // the old distribution's maximum, sum and log-sum; its 26 terms are formed again, one at a time, in the gradient loop
     [[maybe_unused]] const float *zor = zos + (KL ? tid * SK_LOSS_STRIDE : 0);
-    [[maybe_unused]] float Mo = 0.f, So = 0.f, logSo = 0.f, akl = 0.f;
-    [[maybe_unused]] const float ks = a.inv_m * a.kl_coeff;
+    [[maybe_unused]] double Mo = 0.0, So = 0.0, logSo = 0.0, akl = 0.0;
+    [[maybe_unused]] const double ks = inv_m * (double)a.kl_coeff;
     if constexpr (KL) {
-      Mo = zor[0];
+      Mo = (double)zor[0];
 #pragma unroll
-      for (int k = 1; k < K; k++) Mo = fmaxf(Mo, zor[k]);
+      for (int k = 1; k < K; k++) Mo = fmax(Mo, (double)zor[k]);
 #pragma unroll
-      for (int k = 0; k < K; k++) So += expf(zor[k] - Mo);
-      logSo = logf(So);
+      for (int k = 0; k < K; k++) So += exp((double)zor[k] - Mo);
+      logSo = log(So);
     }
 #pragma unroll
     for (int k = 0; k < K; k++) {
-      float g = k == ai ? -(gs * q) : gs * p[k];
-      if (p[k] > 0.f) g += es * (p[k] * (z[k] + H));
-      else if (k != ai) g = 0.f;
+      double g = k == ai ? -(gs * q) : gs * p[k];
+      if (p[k] > 0.0) g += es * (p[k] * (z[k] + H));
+      else if (k != ai) g = 0.0;
       if constexpr (KL) {
         // po_k == 0 exactly at a masked k (as p_k): no term there; z[k] = logp_k is finite wherever po_k > 0, also where p_k is 0
-        const float zo = zor[k] - Mo, po = expf(zo) / So;
-        if (po > 0.f) akl += po * ((zo - logSo) - z[k]);
+        const double zo = (double)zor[k] - Mo, po = exp(zo) / So;
+        if (po > 0.0) akl += po * ((zo - logSo) - z[k]);
         if (a.kl_coeff != 0.f) g += ks * (p[k] - po);
       }
-      zr[k] = g;
+      zr[k] = (float)g;
     }
-    const float d1 = v - vt;
-    float vl = d1 * d1, d = 2.f * d1;
+    const double d1 = v - vt;
+    double vl = d1 * d1, d = 2.0 * d1;
     if (a.vf_clip > 0.f) {
-      const float dv = v - vo;
-      const float vc = vo + fminf(fmaxf(dv, -a.vf_clip), a.vf_clip);
-      const float d2 = vc - vt, vl2 = d2 * d2;
-      if (fabsf(dv) > a.vf_clip && !(vl >= vl2)) d = 0.f;
-      vl = fmaxf(vl, vl2);
+      const double dv = v - vo, c = (double)a.vf_clip;
+      const double vc = vo + fmin(fmax(dv, -c), c);
+      const double d2 = vc - vt, vl2 = d2 * d2;
+      if (fabs(dv) > c && !(vl >= vl2)) d = 0.0;
+      vl = fmax(vl, vl2);
     }
-    a.g_value[o] = a.inv_m * (a.vf_coef * d);
-    st[1] = (double)pl, st[2] = (double)vl, st[3] = (double)H;
+    a.g_value[o] = (float)(inv_m * ((double)a.vf_coef * d));
+    st[1] = pl, st[2] = vl, st[3] = H;
     st[0] = (st[1] + (double)a.vf_coef * st[2]) - (double)a.ent_coef * st[3];
-    st[4] = (double)lp_old - (double)lp;
+    st[4] = lp_old - lp;
     st[5] = clipped ? 1.0 : 0.0;
     if constexpr (KL) {
-      st[6] = (double)akl;
+      st[6] = akl;
       if (a.kl_coeff != 0.f) st[0] += (double)a.kl_coeff * st[6];
     }
   }

@@ -16,8 +16,10 @@ the log-mask - the clipped surrogate, the squared value error and the entropy of
 with ``r = exp(logp[action] - logp_old)``, ``vl = (v - vt)^2`` and ``H`` the entropy of the masked distribution.  ``vf_clip`` is
 RLlib's ``vf_clip_param`` form: ``vl = max(vl, (vc - vt)^2)`` with ``vc = v_old + clamp(v - v_old, -vf_clip, vf_clip)``.  ray is not
 installed where this package is developed: that form is restated from memory of RLlib's torch policy, not checked against it (as
-``action_mask_model.py`` says of ``TorchFC``).  The gradients are the ones torch's autograd gives for the same expression; the
-statistics are means over the rows, accumulated in double in a fixed order - the same input gives the same bits on every call.
+``action_mask_model.py`` says of ``TorchFC``).  The gradients are the ones torch's autograd gives for the same expression; a row is
+evaluated in double from its float32 inputs and every output rounded once (the device's float32 ``logf`` is biased by -7e-08 on a
+softmax's sum, which no mean over rows removes); the statistics are means over the rows, accumulated in double in a fixed order - the
+same input gives the same bits on every call.
 
 ``ppo_loss_kl`` (``skyjo_vec_ppo_loss_kl``) is the same head with the term RLlib's DEFAULT PPO loss carries besides - the reference leaves
 ``ppo.DEFAULT_CONFIG`` as it is, ``kl_coeff`` 0.2 and ``kl_target`` 0.01 with it::
