@@ -497,6 +497,16 @@ void sko_vec_observe(const sko_vec *v, const int32_t *players, int8_t *obs, int8
   }
 }
 
+uint64_t sko_vec_reshuffles(const sko_vec *v, uint64_t *total_out, uint32_t *episode_out) {
+  uint64_t sum = 0;
+  for (int i = 0; i < v->num_envs; i++) {
+    sum += v->games[i].reshuffles_total;
+    if (total_out) total_out[i] = v->games[i].reshuffles_total;
+    if (episode_out) episode_out[i] = v->games[i].reshuffles;
+  }
+  return sum;
+}
+
 /* uniform choice over legal actions == policy_ra's p = mask / sum(mask)
  * (random_admissible_policy.py:26-28), drawn from Philox4x32-10 keyed by the policy seed:
  * ctr = (iter >> 2, game id lo, game id hi, 'POL\0'), word iter & 3, k = mulhi(word, n_legal). */

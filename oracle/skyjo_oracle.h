@@ -139,6 +139,9 @@ void sko_vec_rollout(sko_vec *v, int iters, uint64_t policy_seed, int32_t *actio
 void sko_vec_rollout_rec(sko_vec *v, int iters, uint64_t policy_seed, int32_t *actions_out, int8_t *obs_out, int8_t *mask_out,
                          uint8_t *meta_out, uint16_t *eplen_out, int threads); /* + every iteration's record */
 int sko_policy_action(uint64_t policy_seed, uint64_t game_id, uint64_t iter, const int8_t *mask);
+/* mid-game reshuffles (skyjo.py:361-365) of every game since it was seeded, summed; total_out / episode_out: NULL, or per game the
+ * same count and the count inside the running episode */
+uint64_t sko_vec_reshuffles(const sko_vec *v, uint64_t *total_out, uint32_t *episode_out);
 
 #ifdef __cplusplus
 }

@@ -82,7 +82,9 @@ def lib():
         L.sko_vec_rollout.argtypes = [C.POINTER(Vec), C.c_int, C.c_uint64, C.c_void_p, C.c_int]
         L.sko_vec_rollout_rec.argtypes = [C.POINTER(Vec), C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int]
-        L.sko_policy_action.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.sko_vec_reshuffles.restype = C.c_uint64
+        L.sko_vec_reshuffles.argtypes = [C.POINTER(Vec), C.c_void_p, C.c_void_p]
+        L.sko_policy_action.argtypes =[C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
         L.sko_final_rewards.argtypes = [C.POINTER(Game), C.c_double, C.c_double, C.c_void_p]
         L.sko_evaluate_game.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
         L.sko_set_state.argtypes = [C.POINTER(Game), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
@@ -263,7 +265,14 @@ class OracleVec:
     def counters(self):
         c = self.v.contents
         return dict(steps=c.steps, episodes=c.episodes, illegal=c.illegal, resets=c.resets, sum_len=c.sum_len,
-                    iter=c.iter)
+                    iter=c.iter, reshuffles=int(self.L.sko_vec_reshuffles(self.v, None, None)))
+
+    def reshuffles(self):
+        """Mid-game reshuffles per game: (since the game was seeded uint64 [B], inside its running episode uint32 [B])."""
+        total = np.zeros(self.num_envs, dtype=np.uint64)
+        episode = np.zeros(self.num_envs, dtype=np.uint32)
+        self.L.sko_vec_reshuffles(self.v, _p(total), _p(episode))
+        return total, episode
 
 
 def policy_action(policy_seed, game_id, it, mask):
