@@ -13,7 +13,7 @@ import torch
 from skyjo_rl_amd._lib import TGT_HAS_TARGET
 from skyjo_rl_amd.action_mask_model import FLOAT_MIN, FusedNet
 from skyjo_rl_amd.learner import STATS, STATS_KL, KLCoeff, NativeBranch, PPOLossBuffers, PPOLossKLBuffers, ppo_loss, ppo_loss_kl
-from skyjo_rl_amd.rollout import behaviour_logits, compute_targets, minibatches, select_rows
+from skyjo_rl_amd.rollout import Minibatch, behaviour_logits, compute_targets, minibatches, select_rows
 
 
 @torch.no_grad()
@@ -37,141 +37,100 @@ def compute_returns(buf):
     return returns, mask
 
 
-def _ppo_update_native(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, seats=None):
-    """``ppo_update(..., native_batches=True)``: the same epochs on minibatches the package builds on the buffer as it lies."""
+_TORCH_STATS = ("policy_loss", "vf_loss", "kl")  # what the torch loss reports, in the order of ``_torch_read``
+_REPORTED = _TORCH_STATS + ("entropy", "clip_fraction", "action_kl")  # an epoch's statistics: those of these the loss has
+
+
+def _torch_batches(buf, minibatch, seed, gae):
+    """The torch batch source: the columns of ``buf.views()``, the ``nonzero`` index of the rows with a target and per epoch a
+    ``randperm`` of it, every slice as a ``rollout.Minibatch`` (``values`` and ``seats`` None: the torch loss reads neither).  Returns
+    ``(epoch, transitions)``; ``epoch()`` yields one epoch's minibatches."""
+    v = buf.views()
+    T = buf.T
+    if gae is None:
+        returns, mask = compute_returns(buf)
+    else:
+        compute_targets(buf, gamma=gae[0], lam=gae[1])
+        returns, mask = buf.value_targets, (buf.target_flags & TGT_HAS_TARGET) != 0
+    idx = mask.reshape(-1).nonzero().squeeze(1)
+    obs = v.observations[:T].reshape(-1, v.observations.shape[-1])
+    am = v.action_mask[:T].reshape(-1, 26)
+    act = buf.actions.reshape(-1).long()
+    logp_old = buf.logp.reshape(-1)
+    val_old = buf.values[:T].reshape(-1)
+    ret = returns.reshape(-1)
+    adv_all = ret - val_old if gae is None else buf.advantages.reshape(-1)
+    mean, std = adv_all[idx].mean(), adv_all[idx].std().clamp_min(1e-6)
+    gen = torch.Generator(device=idx.device).manual_seed(seed)
+
+    def epoch():
+        perm = idx[torch.randperm(idx.numel(), device=idx.device, generator=gen)]
+        for k in range(0, perm.numel(), minibatch):
+            j = perm[k:k + minibatch]
+            # log(1) = 0 and log(0) = -inf clamped to FLOAT_MIN: the two values ``gather_rows`` writes
+            yield Minibatch(obs[j].to(torch.float32), torch.clamp(torch.log(am[j].to(torch.float32)), min=FLOAT_MIN), act[j], logp_old[j],
+                            (adv_all[j] - mean) / std, ret[j], None, None)
+
+    return epoch, int(idx.numel())
+
+
+def _native_batches(buf, minibatch, seed, gae, seats, behaviour):
+    """The native batch source: ``rollout.minibatches`` on the buffer as it lies - with ``behaviour``, ``(minibatch, old_logits)``.
+    Returns ``(epoch, transitions)`` as ``_torch_batches`` does."""
     compute_targets(buf, gamma=gae[0], lam=gae[1])
     sel = select_rows(buf, TGT_HAS_TARGET, seats=seats)
     norm = (sel.mean, max(sel.std, 1e-6))
     gen = torch.Generator(device=buf.actions.device).manual_seed(seed)
-    stats = []
-    for ep in range(epochs):
-        tot = {"policy_loss": 0.0, "vf_loss": 0.0, "kl": 0.0, "n": 0}
-        for mb in minibatches(buf, minibatch, generator=gen, normalize=norm, selection=sel):
-            logits = model.policy(mb.observations) + mb.log_mask  # action_mask_model.py:70-71
-            logp = torch.log_softmax(logits, -1).gather(1, mb.actions.unsqueeze(1)).squeeze(1)
-            value = model.value(mb.observations).squeeze(-1)
-            ratio = torch.exp(logp - mb.logp)
-            pl = -torch.min(ratio * mb.advantages, torch.clamp(ratio, 1 - clip, 1 + clip) * mb.advantages).mean()
-            vl = ((value - mb.value_targets) ** 2).mean()
-            loss = pl + vf_coef * vl
-            optimizer.zero_grad(set_to_none=True)
-            loss.backward()
-            optimizer.step()
-            n = mb.actions.numel()
-            tot["policy_loss"] += float(pl.detach()) * n
-            tot["vf_loss"] += float(vl.detach()) * n
-            tot["kl"] += float((mb.logp - logp).mean().detach()) * n
-            tot["n"] += n
-        stats.append({k: tot[k] / max(tot["n"], 1) for k in ("policy_loss", "vf_loss", "kl")})
-    return {"first": stats[0], "last": stats[-1], "transitions": sel.count}
+    kw = {"behaviour": True} if behaviour else {}
+    return (lambda: minibatches(buf, minibatch, generator=gen, normalize=norm, selection=sel, **kw)), sel.count
 
 
-def _ppo_update_native_loss(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip, seats=None):
-    """``ppo_update(..., native_batches=True, native_loss=True)``: the minibatches AND the loss head in native calls
-    (``learner.ppo_loss``: loss, statistics and the gradients with respect to the model's two outputs in one kernel); autograd runs
-    through the two branches only, and the statistics stay on the device until the epoch is over - one read per epoch."""
-    compute_targets(buf, gamma=gae[0], lam=gae[1])
-    sel = select_rows(buf, TGT_HAS_TARGET, seats=seats)
-    norm = (sel.mean, max(sel.std, 1e-6))
-    gen = torch.Generator(device=buf.actions.device).manual_seed(seed)
-    out = PPOLossBuffers(max(min(minibatch, sel.count), 1), buf.actions.device)
-    stats = []
-    for ep in range(epochs):
-        tot = torch.zeros((6,), dtype=torch.float64, device=buf.actions.device)
-        rows = 0
-        for mb in minibatches(buf, minibatch, generator=gen, normalize=norm, selection=sel):
-            logits = model.policy(mb.observations)  # (the kernel adds the mask: action_mask_model.py:70-71)
-            value = model.value(mb.observations)
-            res = ppo_loss(logits, value, mb, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, vf_clip=vf_clip, out=out)
-            optimizer.zero_grad(set_to_none=True)
-            torch.autograd.backward([logits, value], [res.grad_logits, res.grad_value])
-            optimizer.step()
-            n = mb.actions.numel()
-            tot += res.stats * n
-            rows += n
-        host = (tot / max(rows, 1)).tolist()  # the epoch's one read
-        stats.append({k: host[STATS.index(k)] for k in ("policy_loss", "vf_loss", "kl", "entropy", "clip_fraction")})
-    return {"first": stats[0], "last": stats[-1], "transitions": sel.count}
+def _torch_loss(model, mb, clip, vf_coef):
+    """The torch loss on a ``Minibatch`` of either source: (loss, policy loss, value loss, logp of the actions taken)."""
+    logits = model.policy(mb.observations) + mb.log_mask  # action_mask_model.py:70-71
+    logp = torch.log_softmax(logits, -1).gather(1, mb.actions.unsqueeze(1)).squeeze(1)
+    value = model.value(mb.observations).squeeze(-1)
+    ratio = torch.exp(logp - mb.logp)
+    pl = -torch.min(ratio * mb.advantages, torch.clamp(ratio, 1 - clip, 1 + clip) * mb.advantages).mean()
+    vl = ((value - mb.value_targets) ** 2).mean()
+    return pl + vf_coef * vl, pl, vl, logp
 
 
-def _ppo_update_native_nets(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip, seats=None):
-    """``ppo_update(..., native_batches=True, native_loss=True, native_nets=True)``: the two branches as well - per minibatch gather,
-    two forwards, the loss head, two backwards and the optimizer's step, every one a native call (``learner.NativeBranch``): no autograd
-    graph, no allocation inside the loop, no ``zero_grad`` (``backward`` overwrites the gradients)."""
-    compute_targets(buf, gamma=gae[0], lam=gae[1])
-    sel = select_rows(buf, TGT_HAS_TARGET, seats=seats)
-    norm = (sel.mean, max(sel.std, 1e-6))
-    gen = torch.Generator(device=buf.actions.device).manual_seed(seed)
-    rows = max(min(minibatch, sel.count), 1)
-    out = PPOLossBuffers(rows, buf.actions.device)
-    policy, value_branch = NativeBranch(model.policy, rows), NativeBranch(model.value, rows)
-    stats = []
-    for ep in range(epochs):
-        tot = torch.zeros((6,), dtype=torch.float64, device=buf.actions.device)
-        seen = 0
-        for mb in minibatches(buf, minibatch, generator=gen, normalize=norm, selection=sel):
-            logits = policy.forward(mb.observations)  # (the kernel adds the mask: action_mask_model.py:70-71)
-            value = value_branch.forward(mb.observations)
-            res = ppo_loss(logits, value, mb, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, vf_clip=vf_clip, out=out)
-            policy.backward(res.grad_logits)
-            value_branch.backward(res.grad_value)
-            optimizer.step()
-            n = mb.actions.numel()
-            tot += res.stats * n
-            seen += n
-        host = (tot / max(seen, 1)).tolist()  # the epoch's one read
-        stats.append({k: host[STATS.index(k)] for k in ("policy_loss", "vf_loss", "kl", "entropy", "clip_fraction")})
-    return {"first": stats[0], "last": stats[-1], "transitions": sel.count}
+def _torch_read(out, mb):
+    """``_TORCH_STATS`` of a ``_torch_loss``: three reads as Python floats, as a host tensor for the epoch's sum (double products and
+    sums, as Python's own)."""
+    _, pl, vl, logp = out
+    return torch.tensor([float(pl.detach()), float(vl.detach()), float((mb.logp - logp).mean().detach())], dtype=torch.float64)
 
 
-def _ppo_update_kl(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip, native_nets, kl, behaviour_net,
-                   seats=None):
-    """``ppo_update(..., native_loss=True, kl=...)``: the epochs of ``_ppo_update_native_loss`` (or, with ``native_nets``, of
-    ``_ppo_update_native_nets``) with RLlib's KL penalty - ``rollout.behaviour_logits`` once, before the first step changes (and a
-    ``NativeAdam`` re-packs) the net that played, then ``minibatches(behaviour=True)`` and ``learner.ppo_loss_kl``.  The coefficient
-    is constant during the call; a ``KLCoeff`` is updated once, after the last epoch, from the row-weighted mean ``action_kl`` over
-    every minibatch of the call (as RLlib averages its learner statistics over the SGD phase before ``update_kl`` - from memory)."""
-    coeff = float(kl)
-    behaviour_logits(buf, behaviour_net)
-    compute_targets(buf, gamma=gae[0], lam=gae[1])
-    sel = select_rows(buf, TGT_HAS_TARGET, seats=seats)
-    norm = (sel.mean, max(sel.std, 1e-6))
-    dev = buf.actions.device
-    gen = torch.Generator(device=dev).manual_seed(seed)
-    rows = max(min(minibatch, sel.count), 1)
-    out = PPOLossKLBuffers(rows, dev)
-    if native_nets:
-        policy, value_branch = NativeBranch(model.policy, rows), NativeBranch(model.value, rows)
+def _epochs(epochs, batches, names, evaluate, read, optimizer, device, transitions, kl):
+    """THE loop of ``ppo_update``.  ``batches()`` yields an epoch's minibatches (with ``kl``, paired with the old logits),
+    ``evaluate(mb, old_logits)`` runs the model and the loss and leaves the gradients with the parameters, ``read(out, mb)`` is what
+    it returned as a float64 vector of the statistics ``names`` on ``device``: summed there times the rows and read once per epoch.
+    A ``KLCoeff`` is updated once, after the last epoch, from the row-weighted mean ``action_kl`` over every minibatch of the call (as
+    RLlib averages its learner statistics over the SGD phase before ``update_kl`` - from memory)."""
     stats = []
     total_kl, total_rows = 0.0, 0  # host floats, from the epochs' reads: no synchronisation of their own
     for ep in range(epochs):
-        tot = torch.zeros((7,), dtype=torch.float64, device=dev)
+        tot = torch.zeros((len(names),), dtype=torch.float64, device=device)
         seen = 0
-        for mb, old_logits in minibatches(buf, minibatch, generator=gen, normalize=norm, selection=sel, behaviour=True):
-            if native_nets:
-                logits, value = policy.forward(mb.observations), value_branch.forward(mb.observations)
-            else:
-                logits, value = model.policy(mb.observations), model.value(mb.observations)
-            res = ppo_loss_kl(logits, value, mb, old_logits, kl_coeff=coeff, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, vf_clip=vf_clip,
-                              out=out)
-            if native_nets:
-                policy.backward(res.grad_logits)
-                value_branch.backward(res.grad_value)
-            else:
-                optimizer.zero_grad(set_to_none=True)
-                torch.autograd.backward([logits, value], [res.grad_logits, res.grad_value])
+        for item in batches():
+            mb, old_logits = (item, None) if kl is None else item
+            out = evaluate(mb, old_logits)
             optimizer.step()
             n = mb.actions.numel()
-            tot += res.stats * n
+            tot += read(out, mb) * n
             seen += n
         host = (tot / max(seen, 1)).tolist()  # the epoch's one read
-        total_kl += host[6] * seen
-        total_rows += seen
-        stats.append({k: host[STATS_KL.index(k)] for k in ("policy_loss", "vf_loss", "kl", "entropy", "clip_fraction", "action_kl")})
-    mean_kl = total_kl / max(total_rows, 1)
-    if isinstance(kl, KLCoeff) and total_rows:
-        coeff = kl.update(mean_kl)
-    return {"first": stats[0], "last": stats[-1], "transitions": sel.count, "mean_action_kl": mean_kl, "kl_coeff": coeff}
+        stats.append({k: host[names.index(k)] for k in _REPORTED if k in names})
+        if kl is not None:
+            total_kl += stats[-1]["action_kl"] * seen
+            total_rows += seen
+    result = {"first": stats[0], "last": stats[-1], "transitions": transitions}
+    if kl is not None:
+        mean_kl = total_kl / max(total_rows, 1)
+        result.update(mean_action_kl=mean_kl, kl_coeff=kl.update(mean_kl) if isinstance(kl, KLCoeff) and total_rows else float(kl))
+    return result
 
 
 def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_coef=1.0, seed=0, gae=None, native_batches=False,
@@ -202,70 +161,67 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
             raise ValueError("kl needs native_batches=True, native_loss=True and gae=(gamma, lambda)")
         if not isinstance(behaviour_net, FusedNet):
             raise ValueError("kl needs behaviour_net: the policy FusedNet that filled the buffer")
-        return _ppo_update_kl(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip, native_nets, kl,
-                              behaviour_net, seats=seats)
-    if behaviour_net is not None:
-        raise ValueError("behaviour_net belongs to kl")
-    if seats is not None and not native_batches:
-        raise ValueError("seats belongs to native_batches=True")
-    if native_nets and not native_loss:
-        raise ValueError("native_nets=True needs native_loss=True")
-    if native_loss:
-        if not native_batches:
-            raise ValueError("native_loss=True needs native_batches=True")
-        if gae is None:
-            raise ValueError("native_batches=True needs gae=(gamma, lambda)")
-        if native_nets:
-            return _ppo_update_native_nets(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip, seats=seats)
-        return _ppo_update_native_loss(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, ent_coef, vf_clip, seats=seats)
-    if ent_coef != 0.0 or vf_clip is not None:
-        raise ValueError("ent_coef and vf_clip belong to native_loss=True")
-    if native_batches:
-        if gae is None:
-            raise ValueError("native_batches=True needs gae=(gamma, lambda)")
-        return _ppo_update_native(model, buf, optimizer, epochs, minibatch, clip, vf_coef, seed, gae, seats=seats)
-    v = buf.views()
-    T = buf.T
-    if gae is None:
-        returns, mask = compute_returns(buf)
     else:
-        compute_targets(buf, gamma=gae[0], lam=gae[1])
-        returns, mask = buf.value_targets, (buf.target_flags & TGT_HAS_TARGET) != 0
-    idx = mask.reshape(-1).nonzero().squeeze(1)
-    obs = v.observations[:T].reshape(-1, v.observations.shape[-1])
-    am = v.action_mask[:T].reshape(-1, 26)
-    act = buf.actions.reshape(-1).long()
-    logp_old = buf.logp.reshape(-1)
-    val_old = buf.values[:T].reshape(-1)
-    ret = returns.reshape(-1)
-    adv_all = ret - val_old if gae is None else buf.advantages.reshape(-1)
-    mean, std = adv_all[idx].mean(), adv_all[idx].std().clamp_min(1e-6)
-    gen = torch.Generator(device=idx.device).manual_seed(seed)
-    stats = []
-    for ep in range(epochs):
-        perm = idx[torch.randperm(idx.numel(), device=idx.device, generator=gen)]
-        tot = {"policy_loss": 0.0, "vf_loss": 0.0, "kl": 0.0, "n": 0}
-        for k in range(0, perm.numel(), minibatch):
-            j = perm[k:k + minibatch]
-            x = obs[j].to(torch.float32)
-            logits = model.policy(x) + torch.clamp(torch.log(am[j].to(torch.float32)), min=FLOAT_MIN)  # action_mask_model.py:70-71
-            logp = torch.log_softmax(logits, -1).gather(1, act[j].unsqueeze(1)).squeeze(1)
-            value = model.value(x).squeeze(-1)
-            ratio = torch.exp(logp - logp_old[j])
-            adv = (adv_all[j] - mean) / std
-            pl = -torch.min(ratio * adv, torch.clamp(ratio, 1 - clip, 1 + clip) * adv).mean()
-            vl = ((value - ret[j]) ** 2).mean()
-            loss = pl + vf_coef * vl
+        if behaviour_net is not None:
+            raise ValueError("behaviour_net belongs to kl")
+        if seats is not None and not native_batches:
+            raise ValueError("seats belongs to native_batches=True")
+        if native_nets and not native_loss:
+            raise ValueError("native_nets=True needs native_loss=True")
+        if native_loss and not native_batches:
+            raise ValueError("native_loss=True needs native_batches=True")
+        if not native_loss and (ent_coef != 0.0 or vf_clip is not None):
+            raise ValueError("ent_coef and vf_clip belong to native_loss=True")
+        if native_batches and gae is None:
+            raise ValueError("native_batches=True needs gae=(gamma, lambda)")
+    if kl is not None:
+        coeff = float(kl)  # constant during the call
+        behaviour_logits(buf, behaviour_net)  # before the first step changes (and a NativeAdam re-packs) the net that played
+    # where a minibatch comes from
+    if native_batches:
+        batches, transitions = _native_batches(buf, minibatch, seed, gae, seats, kl is not None)
+    else:
+        batches, transitions = _torch_batches(buf, minibatch, seed, gae)
+    # which loss is evaluated: the torch expressions, whose gradients reach the parameters through their own graph ...
+    if not native_loss:
+        def evaluate(mb, old_logits):
+            out = _torch_loss(model, mb, clip, vf_coef)
             optimizer.zero_grad(set_to_none=True)
-            loss.backward()
-            optimizer.step()
-            n = j.numel()
-            tot["policy_loss"] += float(pl.detach()) * n
-            tot["vf_loss"] += float(vl.detach()) * n
-            tot["kl"] += float((logp_old[j] - logp).mean().detach()) * n
-            tot["n"] += n
-        stats.append({k: tot[k] / max(tot["n"], 1) for k in ("policy_loss", "vf_loss", "kl")})
-    return {"first": stats[0], "last": stats[-1], "transitions": int(idx.numel())}
+            out[0].backward()
+            return out
+
+        return _epochs(epochs, batches, _TORCH_STATS, evaluate, _torch_read, optimizer, "cpu", transitions, None)
+    # ... or the native head (the kernel adds the mask: action_mask_model.py:70-71): no allocation inside the loop, one read per epoch
+    dev, rows = buf.actions.device, max(min(minibatch, transitions), 1)
+    out = (PPOLossBuffers if kl is None else PPOLossKLBuffers)(rows, dev)
+    head = dict(clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, vf_clip=vf_clip, out=out)
+    if kl is None:
+        loss = lambda logits, value, mb, old_logits: ppo_loss(logits, value, mb, **head)
+    else:
+        loss = lambda logits, value, mb, old_logits: ppo_loss_kl(logits, value, mb, old_logits, kl_coeff=coeff, **head)
+    # how its gradients reach the parameters
+    if native_nets:
+        # the branches' own kernels: every call of a step native, no autograd graph, no ``zero_grad`` (``backward`` overwrites the gradients)
+        policy, value_branch = NativeBranch(model.policy, rows), NativeBranch(model.value, rows)
+        forward = lambda obs: (policy.forward(obs), value_branch.forward(obs))
+
+        def backward(logits, value, res):
+            policy.backward(res.grad_logits)
+            value_branch.backward(res.grad_value)
+    else:
+        forward = lambda obs: (model.policy(obs), model.value(obs))  # autograd runs through the two branches only
+
+        def backward(logits, value, res):
+            optimizer.zero_grad(set_to_none=True)
+            torch.autograd.backward([logits, value], [res.grad_logits, res.grad_value])
+
+    def evaluate(mb, old_logits):
+        logits, value = forward(mb.observations)
+        res = loss(logits, value, mb, old_logits)
+        backward(logits, value, res)
+        return res
+
+    return _epochs(epochs, batches, STATS if kl is None else STATS_KL, evaluate, lambda res, mb: res.stats, optimizer, dev, transitions, kl)
 
 
 def ppo_update_per_seat(models, buf, optimizers, gae=(0.99, 1.0), native_loss=True, native_nets=False, kls=None, behaviour_nets=None, **kw):

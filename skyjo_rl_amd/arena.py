@@ -95,8 +95,7 @@ def _check_buffer(env, buf):
     from . import rollout
 
     rollout._check_records(buf)
-    if buf.planar != (env.record_layout == "tile-planar-all"):
-        raise ValueError(f"buf.planar={buf.planar}, but the engine's record layout is {env.record_layout!r}")
+    rollout._check_layout(env, buf)
     if buf.B != env.num_envs or buf.N != env.num_players:
         raise ValueError("buf was made for another engine shape")
 
@@ -106,6 +105,8 @@ def select(env, seats, records, seed=0, ticket=0, actions=None, planar=False, wo
     game's record expects.  ``records``: one iteration's records of ``env`` - [num_envs, record_bytes], or with ``planar`` one
     tile-planar block [tiles, P, 64, 16], read in place.  ``seats``: as for ``seat_policies`` (or its result).  ``workspace``: an
     object to cache the logits' workspace on (default: the seat array)."""
+    from .rollout import _layout
+
     torch = env._torch()
     sp = _seats(env, seats)
     _check_iteration(env, records, planar)
@@ -114,7 +115,7 @@ def select(env, seats, records, seed=0, ticket=0, actions=None, planar=False, wo
     elif actions.dtype != torch.int32 or actions.numel() != env.num_envs or not actions.is_contiguous():
         raise ValueError("actions must be a contiguous int32 tensor of num_envs elements")
     ws, nbytes = _workspace(env, sp if workspace is None else workspace, sp)
-    _lib.check(_lib.load().skyjo_vec_arena_select(env._h, sp, C.c_void_p(records.data_ptr()), _lib.REC_TILE_PLANAR if planar else _lib.REC_ROW_MAJOR,
+    _lib.check(_lib.load().skyjo_vec_arena_select(env._h, sp, C.c_void_p(records.data_ptr()), _layout(planar),
                                                   int(seed), int(ticket), C.c_void_p(actions.data_ptr()), ws, nbytes, env._stream()))
     return actions
 
@@ -173,6 +174,8 @@ def act(env, seats, values, records, seed=0, ticket=0, actions=None, logp=None, 
     ``workspace``: as for ``select``; ``values``: ``num_players`` entries, each a ``FusedNet`` of a value branch or None (or the
     result of ``value_nets``).  ``values_only``: no action is chosen and no policy net runs - ``(None, None, values_out)``, the
     bootstrap values of the records a rollout ends on."""
+    from .rollout import _layout
+
     torch = env._torch()
     sp, vn = _seats(env, seats), _values(env, values)
     _check_iteration(env, records, planar)
@@ -192,7 +195,7 @@ def act(env, seats, values, records, seed=0, ticket=0, actions=None, logp=None, 
     values_out = column("values_out", values_out, torch.float32)
     ws, nbytes = _workspace(env, sp if workspace is None else workspace, sp, vn)
     vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    _lib.check(_lib.load().skyjo_vec_arena_act(env._h, sp, vn, vp(records), _lib.REC_TILE_PLANAR if planar else _lib.REC_ROW_MAJOR, int(seed),
+    _lib.check(_lib.load().skyjo_vec_arena_act(env._h, sp, vn, vp(records), _layout(planar), int(seed),
                                                int(ticket), vp(actions), vp(logp), vp(values_out), ws, nbytes, env._stream()))
     return actions, logp, values_out
 

@@ -76,6 +76,52 @@ def _column(name, t, dtype, shape, device):
     return t
 
 
+def _ppo_loss(who, cls, logits, value, mb, old_logits, kl_coeff, clip, vf_coef, ent_coef, vf_clip, out):
+    """``ppo_loss`` (``cls`` is ``PPOLossBuffers``) and ``ppo_loss_kl`` (``PPOLossKLBuffers``: ``old_logits`` and ``kl_coeff`` count) under
+    the name ``who``: the checks, the buffers and the native call."""
+    kl = cls is PPOLossKLBuffers
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[1] != NUM_ACTIONS or logits.shape[0] < 1:
+        raise ValueError("logits must be a float32 tensor of shape [m, 26], m >= 1")
+    dev, m, f = logits.device, logits.shape[0], torch.float32
+    if dev.type != "cuda":
+        raise ValueError(who + " runs on the GPU: logits is on " + str(dev))
+    _column("logits", logits, f, (m, NUM_ACTIONS), dev)
+    if not isinstance(value, torch.Tensor) or tuple(value.shape) not in ((m,), (m, 1)):
+        raise ValueError(f"value must have shape [{m}] or [{m}, 1]")
+    _column("value", value, f, tuple(value.shape), dev)
+    if kl:
+        _column("old_logits", old_logits, f, (m, NUM_ACTIONS), dev)
+    _column("mb.log_mask", mb.log_mask, f, (m, NUM_ACTIONS), dev)
+    _column("mb.actions", mb.actions, torch.int64, (m,), dev)
+    for name in ("logp", "advantages", "value_targets", "values"):
+        _column("mb." + name, getattr(mb, name), f, (m,), dev)
+    clip, kl_coeff = float(clip), float(kl_coeff) if kl else None
+    if not (math.isfinite(clip) and clip > 0.0):
+        raise ValueError("clip must be finite and greater than 0")
+    if kl and not (math.isfinite(kl_coeff) and kl_coeff >= 0.0):
+        raise ValueError("kl_coeff must be finite and not negative")
+    vf_clip = 0.0 if vf_clip is None or not math.isfinite(float(vf_clip)) or float(vf_clip) <= 0.0 else float(vf_clip)
+    if out is None:
+        out = cls(m, dev)
+    elif not isinstance(out, cls) or out.rows < m or out.stats.device != dev:
+        raise ValueError(f"out must be a {cls.__name__} of at least m rows on the inputs' device")
+    grad_logits, grad_value = out.grad_logits[:m], out.grad_value[:m]
+    if any(t.data_ptr() % 16 for t in ((logits, mb.log_mask, old_logits) if kl else (logits, mb.log_mask))):
+        raise ValueError(("logits, mb.log_mask and old_logits" if kl else "logits and mb.log_mask")
+                         + " must start on a 16-byte boundary (a slice that starts at an odd row does not)")
+    L = _lib.load()
+    vp = lambda t: t.data_ptr()
+    rows = (vp(value), vp(mb.actions), vp(mb.logp), vp(mb.advantages), vp(mb.value_targets), vp(mb.values), m, clip, float(vf_coef),
+            float(ent_coef), vf_clip)
+    with torch.cuda.device(dev):
+        outs = (vp(grad_logits), vp(grad_value), vp(out.stats), vp(out.scratch), out.scratch.numel() * 8, torch.cuda.current_stream(dev).cuda_stream)
+        if kl:
+            _lib.check(L.skyjo_vec_ppo_loss_kl(vp(logits), vp(mb.log_mask), vp(old_logits), *rows, kl_coeff, *outs))
+        else:
+            _lib.check(L.skyjo_vec_ppo_loss(vp(logits), vp(mb.log_mask), *rows, *outs))
+    return PPOLossResult(out.stats, grad_logits, grad_value.view(value.shape))
+
+
 @torch.no_grad()
 def ppo_loss(logits, value, mb, clip=0.3, vf_coef=1.0, ent_coef=0.0, vf_clip=None, out=None):
     """The loss head on the minibatch ``mb`` (a ``rollout.Minibatch``, or anything with its ``log_mask``, ``actions``, ``logp``,
@@ -86,38 +132,7 @@ def ppo_loss(logits, value, mb, clip=0.3, vf_coef=1.0, ent_coef=0.0, vf_clip=Non
     ``vf_clip``: None, <= 0 or inf - no value clipping.  ``out``: a ``PPOLossBuffers`` of at least m rows whose tensors (and scratch)
     are reused; the results are views of it, valid until the next call with the same ``out``.  ``mb.actions`` must lie in [0, 26) - a
     precondition, not checked (the kernel reads an action outside as 0)."""
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[1] != NUM_ACTIONS or logits.shape[0] < 1:
-        raise ValueError("logits must be a float32 tensor of shape [m, 26], m >= 1")
-    dev, m, f = logits.device, logits.shape[0], torch.float32
-    if dev.type != "cuda":
-        raise ValueError("ppo_loss runs on the GPU: logits is on " + str(dev))
-    _column("logits", logits, f, (m, NUM_ACTIONS), dev)
-    if not isinstance(value, torch.Tensor) or tuple(value.shape) not in ((m,), (m, 1)):
-        raise ValueError(f"value must have shape [{m}] or [{m}, 1]")
-    _column("value", value, f, tuple(value.shape), dev)
-    _column("mb.log_mask", mb.log_mask, f, (m, NUM_ACTIONS), dev)
-    _column("mb.actions", mb.actions, torch.int64, (m,), dev)
-    for name in ("logp", "advantages", "value_targets", "values"):
-        _column("mb." + name, getattr(mb, name), f, (m,), dev)
-    clip = float(clip)
-    if not (math.isfinite(clip) and clip > 0.0):
-        raise ValueError("clip must be finite and greater than 0")
-    vf_clip = 0.0 if vf_clip is None or not math.isfinite(float(vf_clip)) or float(vf_clip) <= 0.0 else float(vf_clip)
-    if out is None:
-        out = PPOLossBuffers(m, dev)
-    elif not isinstance(out, PPOLossBuffers) or out.rows < m or out.stats.device != dev:
-        raise ValueError("out must be a PPOLossBuffers of at least m rows on the inputs' device")
-    grad_logits, grad_value = out.grad_logits[:m], out.grad_value[:m]
-    if any(t.data_ptr() % 16 for t in (logits, mb.log_mask)):
-        raise ValueError("logits and mb.log_mask must start on a 16-byte boundary (a slice that starts at an odd row does not)")
-    L = _lib.load()
-    vp = lambda t: t.data_ptr()
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.skyjo_vec_ppo_loss(vp(logits), vp(mb.log_mask), vp(value), vp(mb.actions), vp(mb.logp), vp(mb.advantages),
-                                        vp(mb.value_targets), vp(mb.values), m, clip, float(vf_coef), float(ent_coef), vf_clip,
-                                        vp(grad_logits), vp(grad_value), vp(out.stats), vp(out.scratch), out.scratch.numel() * 8, stream))
-    return PPOLossResult(out.stats, grad_logits, grad_value.view(value.shape))
+    return _ppo_loss("ppo_loss", PPOLossBuffers, logits, value, mb, None, None, clip, vf_coef, ent_coef, vf_clip, out)
 
 
 @torch.no_grad()
@@ -128,42 +143,7 @@ def ppo_loss_kl(logits, value, mb, old_logits, kl_coeff=0.2, clip=0.3, vf_coef=1
     0.2; ``float(KLCoeff)`` works).  Returns ``PPOLossResult`` with ``stats`` float64 [7] in the order of ``STATS_KL``: the loss includes
     ``kl_coeff * action_kl``, the gradient ``kl_coeff (p - p_old) / m``; ``action_kl`` is computed also when ``kl_coeff`` is 0, where
     everything else carries the bits of ``ppo_loss``.  ``out``: a ``PPOLossKLBuffers``.  Everything else as for ``ppo_loss``."""
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[1] != NUM_ACTIONS or logits.shape[0] < 1:
-        raise ValueError("logits must be a float32 tensor of shape [m, 26], m >= 1")
-    dev, m, f = logits.device, logits.shape[0], torch.float32
-    if dev.type != "cuda":
-        raise ValueError("ppo_loss_kl runs on the GPU: logits is on " + str(dev))
-    _column("logits", logits, f, (m, NUM_ACTIONS), dev)
-    if not isinstance(value, torch.Tensor) or tuple(value.shape) not in ((m,), (m, 1)):
-        raise ValueError(f"value must have shape [{m}] or [{m}, 1]")
-    _column("value", value, f, tuple(value.shape), dev)
-    _column("old_logits", old_logits, f, (m, NUM_ACTIONS), dev)
-    _column("mb.log_mask", mb.log_mask, f, (m, NUM_ACTIONS), dev)
-    _column("mb.actions", mb.actions, torch.int64, (m,), dev)
-    for name in ("logp", "advantages", "value_targets", "values"):
-        _column("mb." + name, getattr(mb, name), f, (m,), dev)
-    clip, kl_coeff = float(clip), float(kl_coeff)
-    if not (math.isfinite(clip) and clip > 0.0):
-        raise ValueError("clip must be finite and greater than 0")
-    if not (math.isfinite(kl_coeff) and kl_coeff >= 0.0):
-        raise ValueError("kl_coeff must be finite and not negative")
-    vf_clip = 0.0 if vf_clip is None or not math.isfinite(float(vf_clip)) or float(vf_clip) <= 0.0 else float(vf_clip)
-    if out is None:
-        out = PPOLossKLBuffers(m, dev)
-    elif not isinstance(out, PPOLossKLBuffers) or out.rows < m or out.stats.device != dev:
-        raise ValueError("out must be a PPOLossKLBuffers of at least m rows on the inputs' device")
-    grad_logits, grad_value = out.grad_logits[:m], out.grad_value[:m]
-    if any(t.data_ptr() % 16 for t in (logits, mb.log_mask, old_logits)):
-        raise ValueError("logits, mb.log_mask and old_logits must start on a 16-byte boundary (a slice that starts at an odd row does not)")
-    L = _lib.load()
-    vp = lambda t: t.data_ptr()
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.skyjo_vec_ppo_loss_kl(vp(logits), vp(mb.log_mask), vp(old_logits), vp(value), vp(mb.actions), vp(mb.logp),
-                                           vp(mb.advantages), vp(mb.value_targets), vp(mb.values), m, clip, float(vf_coef), float(ent_coef),
-                                           vf_clip, kl_coeff, vp(grad_logits), vp(grad_value), vp(out.stats), vp(out.scratch),
-                                           out.scratch.numel() * 8, stream))
-    return PPOLossResult(out.stats, grad_logits, grad_value.view(value.shape))
+    return _ppo_loss("ppo_loss_kl", PPOLossKLBuffers, logits, value, mb, old_logits, kl_coeff, clip, vf_coef, ent_coef, vf_clip, out)
 
 
 class KLCoeff:
@@ -194,6 +174,19 @@ class KLCoeff:
         return self.coeff
 
 
+def _head_forward(ctx, res):
+    """What ``PPOLoss.forward`` and ``PPOLossKL.forward`` do with their head's result."""
+    ctx.save_for_backward(res.grad_logits, res.grad_value)
+    ctx.mark_non_differentiable(res.stats)
+    return res.stats[0].to(torch.float32), res.stats
+
+
+def _head_backward(ctx, grad_loss, _grad_stats):
+    """... and their ``backward``: ``logits`` and ``value`` get a gradient, every other input of ``apply`` None."""
+    grad_logits, grad_value = ctx.saved_tensors
+    return (grad_logits * grad_loss, grad_value * grad_loss) + (None,) * (len(ctx.needs_input_grad) - 2)
+
+
 class PPOLoss(torch.autograd.Function):
     """``loss, stats = PPOLoss.apply(logits, value, mb, clip, vf_coef, ent_coef, vf_clip)``: ``ppo_loss`` inside autograd.  ``loss``
     is ``stats[0]`` as a float32 scalar; ``stats`` (float64 [6]) is not differentiable.  Backward hands the gradients the kernel
@@ -201,15 +194,9 @@ class PPOLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, value, mb, clip=0.3, vf_coef=1.0, ent_coef=0.0, vf_clip=None):
-        res = ppo_loss(logits.detach(), value.detach(), mb, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, vf_clip=vf_clip)
-        ctx.save_for_backward(res.grad_logits, res.grad_value)
-        ctx.mark_non_differentiable(res.stats)
-        return res.stats[0].to(torch.float32), res.stats
+        return _head_forward(ctx, ppo_loss(logits.detach(), value.detach(), mb, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, vf_clip=vf_clip))
 
-    @staticmethod
-    def backward(ctx, grad_loss, _grad_stats):
-        grad_logits, grad_value = ctx.saved_tensors
-        return grad_logits * grad_loss, grad_value * grad_loss, None, None, None, None, None
+    backward = staticmethod(_head_backward)
 
 
 class PPOLossKL(torch.autograd.Function):
@@ -218,16 +205,10 @@ class PPOLossKL(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, value, mb, old_logits, kl_coeff=0.2, clip=0.3, vf_coef=1.0, ent_coef=0.0, vf_clip=None):
-        res = ppo_loss_kl(logits.detach(), value.detach(), mb, old_logits.detach(), kl_coeff=kl_coeff, clip=clip, vf_coef=vf_coef,
-                          ent_coef=ent_coef, vf_clip=vf_clip)
-        ctx.save_for_backward(res.grad_logits, res.grad_value)
-        ctx.mark_non_differentiable(res.stats)
-        return res.stats[0].to(torch.float32), res.stats
+        return _head_forward(ctx, ppo_loss_kl(logits.detach(), value.detach(), mb, old_logits.detach(), kl_coeff=kl_coeff, clip=clip,
+                                              vf_coef=vf_coef, ent_coef=ent_coef, vf_clip=vf_clip))
 
-    @staticmethod
-    def backward(ctx, grad_loss, _grad_stats):
-        grad_logits, grad_value = ctx.saved_tensors
-        return grad_logits * grad_loss, grad_value * grad_loss, None, None, None, None, None, None, None
+    backward = staticmethod(_head_backward)
 
 
 class NativeAdam:

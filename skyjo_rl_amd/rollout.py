@@ -58,11 +58,21 @@ class RolloutBuffer:
         return self.views().done[: self.T] == 0
 
 
+def _layout(planar):
+    """The C ABI's record layout constant for ``planar``: the flag, or a buffer that has it."""
+    return _lib.REC_TILE_PLANAR if getattr(planar, "planar", planar) else _lib.REC_ROW_MAJOR
+
+
+def _check_layout(env, buf):
+    """``buf.planar`` is what the engine writes, or ``ValueError``."""
+    if buf.planar != (env.record_layout == "tile-planar-all"):
+        raise ValueError(f"buf.planar={buf.planar}, but the engine's record layout is {env.record_layout!r}")
+
+
 def _check_handoff(env, buf):
     """``buf.planar`` is captured when the buffer is made, the engine reads its layout when it is called, and the native calls take no
     size: a buffer of the other layout would be overrun (num_envs % 64 != 0) or silently filled in the other layout."""
-    if buf.planar != (env.record_layout == "tile-planar-all"):
-        raise ValueError(f"buf.planar={buf.planar}, but the engine's record layout is {env.record_layout!r}")
+    _check_layout(env, buf)
     want = (buf.T + 1) * (env.tiles * 64 if buf.planar else env.num_envs) * env.record_bytes
     r = buf.records
     if r.dtype != torch.uint8 or not r.is_contiguous() or r.numel() != want:
@@ -123,7 +133,7 @@ def compute_targets(buf, gamma=0.99, lam=1.0):
         buf.returns = torch.empty((buf.T, buf.B), dtype=torch.float32, device=dev)
         buf.target_flags = torch.empty((buf.T, buf.B), dtype=torch.uint8, device=dev)
     vp = lambda t: t.data_ptr()
-    _lib.check(L.skyjo_vec_rollout_targets(buf._env._h, vp(buf.records), _lib.REC_TILE_PLANAR if buf.planar else _lib.REC_ROW_MAJOR, buf.T,
+    _lib.check(L.skyjo_vec_rollout_targets(buf._env._h, vp(buf.records), _layout(buf), buf.T,
                                            vp(buf.values), buf.values.shape[-1], vp(buf.final_rewards), vp(buf.episode_end),
                                            float(gamma), float(lam), vp(buf.advantages), vp(buf.value_targets), vp(buf.returns),
                                            vp(buf.target_flags), buf._env._stream()))
@@ -172,6 +182,12 @@ def _check_records(buf):
         raise ValueError(f"buf.records has shape {tuple(r.shape)}, but planar={buf.planar} means {want}")
 
 
+def _check_index(buf, index, tensor=False):
+    """``index`` holds row ids for a gather from ``buf``, or ``ValueError``; ``tensor``: for anything that is no tensor as well."""
+    if (tensor and not isinstance(index, torch.Tensor)) or index.dtype != torch.int64 or index.dim() != 1 or index.device != buf.actions.device:
+        raise ValueError("index must be a one-dimensional int64 tensor on the buffer's device")
+
+
 def _seat_mask(buf, seats):
     """The bit mask of ``seats`` (an iterable of seat numbers below ``buf.N``, at least one), or ``ValueError``."""
     mask = 0
@@ -209,7 +225,7 @@ def select_rows(buf, require=_lib.TGT_HAS_TARGET, seats=None):
         _lib.check(L.skyjo_vec_rollout_select(buf._env._h, buf.target_flags.data_ptr(), n, int(require), buf.advantages.data_ptr(),
                                               buf.row_index.data_ptr(), out.data_ptr(), out[1:].data_ptr(), buf._env._stream()))
     else:
-        _lib.check(L.skyjo_vec_rollout_select_seats(buf._env._h, buf.records.data_ptr(), _lib.REC_TILE_PLANAR if buf.planar else _lib.REC_ROW_MAJOR,
+        _lib.check(L.skyjo_vec_rollout_select_seats(buf._env._h, buf.records.data_ptr(), _layout(buf),
                                                     buf.T, buf.target_flags.data_ptr(), int(require), mask, buf.advantages.data_ptr(),
                                                     buf.row_index.data_ptr(), out.data_ptr(), out[1:].data_ptr(), buf._env._stream()))
     host = out.cpu()
@@ -239,8 +255,7 @@ def gather_rows(buf, index, normalize=None, out=None):
     if getattr(buf, "advantages", None) is None:
         raise ValueError("gather_rows needs the columns of compute_targets(buf)")
     _check_records(buf)
-    if index.dtype != torch.int64 or index.dim() != 1 or index.device != buf.actions.device:
-        raise ValueError("index must be a one-dimensional int64 tensor on the buffer's device")
+    _check_index(buf, index)
     index = index.contiguous()
     m = index.numel()
     mean, std = (0.0, 1.0) if normalize is None else normalize
@@ -250,7 +265,7 @@ def gather_rows(buf, index, normalize=None, out=None):
         raise ValueError("out holds fewer rows than index")
     L = _lib.load()
     vp = lambda t: t.data_ptr()
-    _lib.check(L.skyjo_vec_rollout_gather(buf._env._h, vp(buf.records), _lib.REC_TILE_PLANAR if buf.planar else _lib.REC_ROW_MAJOR, buf.T,
+    _lib.check(L.skyjo_vec_rollout_gather(buf._env._h, vp(buf.records), _layout(buf), buf.T,
                                           vp(index), m, vp(buf.actions), vp(buf.logp), vp(buf.values), buf.values.shape[-1],
                                           vp(buf.advantages), vp(buf.value_targets), float(mean), float(std), vp(out.observations),
                                           vp(out.log_mask), vp(out.actions), vp(out.logp), vp(out.advantages), vp(out.value_targets),
@@ -268,8 +283,7 @@ def gather_behaviour(buf, index, out=None):
     if col is None:
         raise ValueError("gather_behaviour needs the column of behaviour_logits(buf, policy_net)")
     dev = buf.actions.device
-    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1 or index.device != dev:
-        raise ValueError("index must be a one-dimensional int64 tensor on the buffer's device")
+    _check_index(buf, index, tensor=True)
     if col.dtype != torch.float32 or tuple(col.shape) != (buf.T, buf.B, 26) or col.device != dev or not col.is_contiguous():
         raise ValueError(f"buf.behaviour must be a contiguous float32 tensor of shape [{buf.T}, {buf.B}, 26] on {dev}")
     index = index.contiguous()

@@ -105,7 +105,7 @@ def branches(b, clip=CLIP, vf_clip=VF_CLIP):
 
 def torch_head(logits, log_mask, value, actions, logp_old, adv, vt, v_old, clip=CLIP, vf_coef=1.0, ent_coef=0.0, vf_clip=None):
     """The loss head as torch expressions, in the dtype and on the device of its arguments: literally the lines of
-    ``examples/ppo.py::_ppo_update_native`` - extended by ``- ent_coef * entropy`` and the value-clip ``max``.  Returns
+    ``examples/ppo.py::_torch_loss`` - extended by ``- ent_coef * entropy`` and the value-clip ``max``.  Returns
     (loss, stats): stats = [loss, policy_loss, vf_loss, entropy, kl, clip_fraction] as detached scalars."""
     import torch
 

@@ -481,19 +481,47 @@ def test_ppo_update_with_kl_end_to_end(native_nets):
 
 
 def test_ppo_update_without_kl_is_the_path_it_was():
-    """``kl=None`` against the function the default path has always ended in, called directly on a fresh, identically seeded set-up:
-    the same statistics and the same parameters (the all-native path, whose every kernel promises the same bits on every call)."""
+    """``kl=None`` against the all-native path written out here from the package's public pieces, on a fresh, identically seeded
+    set-up: the same statistics and the same parameters (every kernel of that path promises the same bits on every call)."""
     import torch
 
     from examples import ppo
-    from skyjo_rl_amd.learner import NativeAdam
+    from skyjo_rl_amd import _lib
+    from skyjo_rl_amd.learner import STATS, NativeAdam, NativeBranch, PPOLossBuffers, ppo_loss
+    from skyjo_rl_amd.rollout import compute_targets, minibatches, select_rows
+
+    def written_out(model, buf, opt, epochs=2, minibatch=2048):
+        compute_targets(buf, gamma=0.99, lam=1.0)
+        sel = select_rows(buf, _lib.TGT_HAS_TARGET)
+        norm = (sel.mean, max(sel.std, 1e-6))
+        gen = torch.Generator(device=buf.actions.device).manual_seed(0)
+        rows = max(min(minibatch, sel.count), 1)
+        bufs = PPOLossBuffers(rows, buf.actions.device)
+        policy, value = NativeBranch(model.policy, rows), NativeBranch(model.value, rows)
+        stats = []
+        for ep in range(epochs):
+            tot = torch.zeros((6,), dtype=torch.float64, device=buf.actions.device)
+            seen = 0
+            for mb in minibatches(buf, minibatch, generator=gen, normalize=norm, selection=sel):
+                logits = policy.forward(mb.observations)
+                v = value.forward(mb.observations)
+                res = ppo_loss(logits, v, mb, clip=0.3, vf_coef=1.0, ent_coef=0.0, vf_clip=None, out=bufs)
+                policy.backward(res.grad_logits)
+                value.backward(res.grad_value)
+                opt.step()
+                n = mb.actions.numel()
+                tot += res.stats * n
+                seen += n
+            host = (tot / max(seen, 1)).tolist()
+            stats.append({k: host[STATS.index(k)] for k in ("policy_loss", "vf_loss", "kl", "entropy", "clip_fraction")})
+        return {"first": stats[0], "last": stats[-1], "transitions": sel.count}
 
     results, params = [], []
     for direct in (False, True):
         env, model, pol, val, buf = _setup(T=32)
         opt = NativeAdam(model, pol, val, lr=3e-4)
         if direct:
-            out = ppo._ppo_update_native_nets(model, buf, opt, 2, 2048, 0.3, 1.0, 0, (0.99, 1.0), 0.0, None, seats=None)
+            out = written_out(model, buf, opt)
         else:
             out = ppo.ppo_update(model, buf, opt, epochs=2, minibatch=2048, gae=(0.99, 1.0), native_batches=True, native_loss=True,
                                  native_nets=True, kl=None)

@@ -172,3 +172,41 @@ def test_python_surface_and_checks_that_need_no_gpu():
                dict(behaviour_net=object(), native_batches=True, native_loss=True, gae=(0.99, 1.0))):
         with pytest.raises(ValueError):
             ppo.ppo_update(None, None, None, **kw)
+
+
+def test_ppo_update_validation_matrix():
+    """Which combinations of ``ppo_update``'s switches are rejected (``ValueError``) and which get as far as the first use of the
+    ``None`` buffer (anything else): the whole product, 768 combinations, against the rule stated here.  Without ``kl``: no
+    ``behaviour_net``, ``seats`` => ``native_batches``, ``native_nets`` => ``native_loss`` => ``native_batches`` => ``gae``, and an
+    ``ent_coef`` or a ``vf_clip`` => ``native_loss``: 20.  With ``kl`` (a float or a ``KLCoeff``): ``native_batches``, ``native_loss``,
+    ``gae`` and a ``FusedNet`` as ``behaviour_net``, everything else free: 32."""
+    import itertools
+
+    from examples import ppo
+    from skyjo_rl_amd.action_mask_model import FusedNet
+    from skyjo_rl_amd.learner import KLCoeff
+
+    def accepted(gae, batches, loss, nets, ent_coef, vf_clip, seats, kl, net):
+        if kl is not None:
+            return batches and loss and gae is not None and net is not None
+        return (net is None and (seats is None or batches) and (not nets or loss) and (not loss or batches)
+                and (not batches or gae is not None) and (loss or (ent_coef == 0.0 and vf_clip is None)))
+
+    net = object.__new__(FusedNet)  # (no handle, no library: only its type is looked at before the buffer is)
+    product = list(itertools.product((None, (0.99, 1.0)), (False, True), (False, True), (False, True), (0.0, 0.01), (None, 1.0), (None, (0,)),
+                                     (None, 0.2, KLCoeff()), (None, net)))
+    assert len(product) == 768
+    count = {False: 0, True: 0}
+    for combo in product:
+        gae, batches, loss, nets, ent_coef, vf_clip, seats, kl, bnet = combo
+        try:
+            ppo.ppo_update(None, None, None, gae=gae, native_batches=batches, native_loss=loss, native_nets=nets, ent_coef=ent_coef,
+                           vf_clip=vf_clip, seats=seats, kl=kl, behaviour_net=bnet)
+            got = None
+        except ValueError:
+            got = False
+        except Exception:
+            got = True
+        assert got is bool(accepted(*combo)), (combo, got)
+        count[kl is not None] += got
+    assert count == {False: 20, True: 32}

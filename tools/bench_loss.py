@@ -1,6 +1,6 @@
 """The PPO loss head on device against the torch expressions it replaces, at the example's minibatch (m = 32 768 rows, 26 actions):
 ``learner.ppo_loss`` (skyjo_vec_ppo_loss: one fused kernel and a single-workgroup reduction - loss, statistics and both gradients)
-and the lines of ``examples/ppo.py::_ppo_update_native`` (mask, log_softmax, gather, exp, clamp, min, means, autograd backwards, and
+and the lines of ``examples/ppo.py::_torch_loss`` (mask, log_softmax, gather, exp, clamp, min, means, autograd backwards, and
 the three ``float(...)`` statistics reads per minibatch), on the same seeded inputs in the same run.  Two measurements, each side
 alternating with the other, ROUNDS rounds of CALLS calls after a warm-up, timed by a host clock around work that ends in a device
 synchronise (the torch side reads statistics back: that stall is part of what it costs):
@@ -43,7 +43,7 @@ def inputs(m, dev, seed=0):
 
 
 def torch_head(logits_raw, value, mb):
-    """``_ppo_update_native``'s lines between the model's outputs and ``loss.backward()``: (loss, pl, vl, logp)."""
+    """``examples/ppo.py::_torch_loss``'s lines between the model's outputs and ``loss.backward()``: (loss, pl, vl, logp)."""
     logits = logits_raw + mb.log_mask
     logp = torch.log_softmax(logits, -1).gather(1, mb.actions.unsqueeze(1)).squeeze(1)
     ratio = torch.exp(logp - mb.logp)
