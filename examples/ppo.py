@@ -8,11 +8,13 @@ Rewards in SkyJo arrive once, at the end of an episode, for every seat (skyjo_en
 set-up every seat is its own agent, so the return of a step is the final reward of the seat that acted (gamma = 1 inside
 an episode).  Steps of episodes that did not finish inside the buffer carry no return and are masked out.
 """
+import math
+
 import torch
 
 from skyjo_rl_amd._lib import TGT_HAS_TARGET
 from skyjo_rl_amd.action_mask_model import FLOAT_MIN, FusedNet
-from skyjo_rl_amd.learner import STATS, STATS_KL, KLCoeff, NativeBranch, PPOLossBuffers, PPOLossKLBuffers, ppo_loss, ppo_loss_kl
+from skyjo_rl_amd.learner import STATS, STATS_KL, KLCoeff, NativeAdam, NativeBranch, PPOLossBuffers, PPOLossKLBuffers, ppo_loss, ppo_loss_kl
 from skyjo_rl_amd.rollout import Minibatch, behaviour_logits, compute_targets, minibatches, select_rows
 
 
@@ -39,6 +41,26 @@ def compute_returns(buf):
 
 _TORCH_STATS = ("policy_loss", "vf_loss", "kl")  # what the torch loss reports, in the order of ``_torch_read``
 _REPORTED = _TORCH_STATS + ("entropy", "clip_fraction", "action_kl")  # an epoch's statistics: those of these the loss has
+_CLIP_STATS = ("grad_norm", "grad_clipped")  # ... and with ``grad_clip`` these two, means over the epoch's steps
+
+
+def _clipped_step(model, optimizer, grad_clip):
+    """``optimizer.step()`` behind the clipping of the gradients by their global norm; returns ``_CLIP_STATS`` of the step as a float64
+    [2] tensor on the parameters' device - the norm before clipping, and 1 where the coefficient was below 1 - without reading it.  A
+    ``NativeAdam`` (its ``max_grad_norm`` is ``grad_clip`` for the step, whatever it was) clips inside its step; for a torch optimizer
+    it is ``torch.nn.utils.clip_grad_norm_`` over the parameters of both branches, whose coefficient is formed here once more."""
+    if isinstance(optimizer, NativeAdam):
+        earlier, optimizer.max_grad_norm = optimizer.max_grad_norm, grad_clip
+        try:
+            optimizer.step()
+            norm, below = optimizer.grad_stats[0], optimizer.grad_stats[1] < 1.0
+        finally:
+            optimizer.max_grad_norm = earlier
+    else:
+        norm = torch.nn.utils.clip_grad_norm_(list(model.policy.parameters()) + list(model.value.parameters()), grad_clip)
+        below = grad_clip / (norm + 1e-6) < 1.0
+        optimizer.step()
+    return torch.stack([norm.to(torch.float64), below.to(torch.float64)])
 
 
 def _torch_batches(buf, minibatch, seed, gae):
@@ -103,26 +125,35 @@ def _torch_read(out, mb):
     return torch.tensor([float(pl.detach()), float(vl.detach()), float((mb.logp - logp).mean().detach())], dtype=torch.float64)
 
 
-def _epochs(epochs, batches, names, evaluate, read, optimizer, device, transitions, kl):
+def _epochs(epochs, batches, names, evaluate, read, step, device, transitions, kl):
     """THE loop of ``ppo_update``.  ``batches()`` yields an epoch's minibatches (with ``kl``, paired with the old logits),
     ``evaluate(mb, old_logits)`` runs the model and the loss and leaves the gradients with the parameters, ``read(out, mb)`` is what
     it returned as a float64 vector of the statistics ``names`` on ``device``: summed there times the rows and read once per epoch.
+    ``step()`` is the optimizer's step; what it returns (None, or ``_clipped_step``'s pair) is summed per step and read with them.
     A ``KLCoeff`` is updated once, after the last epoch, from the row-weighted mean ``action_kl`` over every minibatch of the call (as
     RLlib averages its learner statistics over the SGD phase before ``update_kl`` - from memory)."""
     stats = []
     total_kl, total_rows = 0.0, 0  # host floats, from the epochs' reads: no synchronisation of their own
     for ep in range(epochs):
         tot = torch.zeros((len(names),), dtype=torch.float64, device=device)
-        seen = 0
+        seen, steps, clip_tot = 0, 0, None
         for item in batches():
             mb, old_logits = (item, None) if kl is None else item
             out = evaluate(mb, old_logits)
-            optimizer.step()
+            clipped = step()
             n = mb.actions.numel()
             tot += read(out, mb) * n
             seen += n
-        host = (tot / max(seen, 1)).tolist()  # the epoch's one read
+            if clipped is not None:
+                clip_tot = clipped if clip_tot is None else clip_tot.add_(clipped)
+                steps += 1
+        mean = tot / max(seen, 1)
+        if clip_tot is not None:
+            mean = torch.cat([mean, clip_tot.to(mean.device) / steps])
+        host = mean.tolist()  # the epoch's one read
         stats.append({k: host[names.index(k)] for k in _REPORTED if k in names})
+        if clip_tot is not None:
+            stats[-1].update(zip(_CLIP_STATS, host[len(names):]))
         if kl is not None:
             total_kl += stats[-1]["action_kl"] * seen
             total_rows += seen
@@ -134,7 +165,7 @@ def _epochs(epochs, batches, names, evaluate, read, optimizer, device, transitio
 
 
 def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_coef=1.0, seed=0, gae=None, native_batches=False,
-               native_loss=False, ent_coef=0.0, vf_clip=None, native_nets=False, seats=None, kl=None, behaviour_net=None):
+               native_loss=False, ent_coef=0.0, vf_clip=None, native_nets=False, seats=None, kl=None, behaviour_net=None, grad_clip=None):
     """Clipped-surrogate PPO epochs over the buffer (RLlib defaults: clip_param 0.3, vf_loss_coeff 1.0).  Returns the mean
     losses of the first and the last epoch.  ``gae``: None - Monte-Carlo returns of the episodes that ended inside the buffer
     (``compute_returns``); (gamma, lambda) - advantages, value targets and the row mask of ``rollout.compute_targets`` (one
@@ -153,7 +184,17 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
     ``behaviour_net`` the policy ``FusedNet`` that filled the buffer (of the seats being updated, for an arena buffer).  The epoch
     statistics gain ``action_kl`` and the result ``mean_action_kl`` - the row-weighted mean over every minibatch of the call - and
     ``kl_coeff``: the coefficient AFTER the call, a ``KLCoeff`` having been updated once with that mean.  None: no such term, the
-    paths above."""
+    paths above.  ``grad_clip`` (any path): RLlib's ``grad_clip`` - every step's gradients are scaled by
+    ``min(1, grad_clip / (norm + 1e-6))``, ``norm`` the global L2 norm over the parameters of both branches.  A ``learner.NativeAdam``
+    does it inside its step (its ``max_grad_norm`` is set for the call's steps: one more native launch, no allocation, no synchronisation), a
+    torch optimizer through ``torch.nn.utils.clip_grad_norm_`` between the backward and its step.  The epoch statistics gain
+    ``grad_norm`` - the mean over the epoch's steps of the norm before clipping - and ``grad_clipped``, the share of steps whose
+    coefficient was below 1; both are summed on the device and come with the epoch's read.  None: no clipping, every path and every
+    result as without the keyword."""
+    if grad_clip is not None:
+        if isinstance(grad_clip, bool) or not isinstance(grad_clip, (int, float)) or not (math.isfinite(grad_clip) and grad_clip > 0):
+            raise ValueError("grad_clip must be None or a finite number greater than 0")
+        grad_clip = float(grad_clip)
     if kl is not None:
         if isinstance(kl, bool) or not isinstance(kl, (int, float, KLCoeff)):
             raise ValueError("kl must be None, a float or a learner.KLCoeff")
@@ -177,6 +218,8 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
     if kl is not None:
         coeff = float(kl)  # constant during the call
         behaviour_logits(buf, behaviour_net)  # before the first step changes (and a NativeAdam re-packs) the net that played
+    # the optimizer's step, behind the clipping where there is one
+    step = optimizer.step if grad_clip is None else lambda: _clipped_step(model, optimizer, grad_clip)
     # where a minibatch comes from
     if native_batches:
         batches, transitions = _native_batches(buf, minibatch, seed, gae, seats, kl is not None)
@@ -190,7 +233,7 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
             out[0].backward()
             return out
 
-        return _epochs(epochs, batches, _TORCH_STATS, evaluate, _torch_read, optimizer, "cpu", transitions, None)
+        return _epochs(epochs, batches, _TORCH_STATS, evaluate, _torch_read, step, "cpu", transitions, None)
     # ... or the native head (the kernel adds the mask: action_mask_model.py:70-71): no allocation inside the loop, one read per epoch
     dev, rows = buf.actions.device, max(min(minibatch, transitions), 1)
     out = (PPOLossBuffers if kl is None else PPOLossKLBuffers)(rows, dev)
@@ -221,7 +264,7 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
         backward(logits, value, res)
         return res
 
-    return _epochs(epochs, batches, STATS if kl is None else STATS_KL, evaluate, lambda res, mb: res.stats, optimizer, dev, transitions, kl)
+    return _epochs(epochs, batches, STATS if kl is None else STATS_KL, evaluate, lambda res, mb: res.stats, step, dev, transitions, kl)
 
 
 def ppo_update_per_seat(models, buf, optimizers, gae=(0.99, 1.0), native_loss=True, native_nets=False, kls=None, behaviour_nets=None, **kw):

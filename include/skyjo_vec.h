@@ -412,6 +412,30 @@ int skyjo_vec_episode_ends_layout(skyjo_vec *h, const void *records, int32_t lay
  * SKYJO_E_INVALID (nothing is launched, the net is unchanged): a null pointer, a misaligned array, state_bytes too small, step < 1,
  * lr not finite, beta1 or beta2 outside [0, 1), eps negative or not finite.
  *
+ * skyjo_vec_grad_norm: the global L2 norm of n device float32 arrays and the coefficient torch.nn.utils.clip_grad_norm_ scales by -
+ * what RLlib's PPO clips a policy's gradients with (grad_clip) - in ONE launch of one workgroup of 1024 threads on `stream`, on the
+ * current device; the job is a branch pair's twelve gradient tensors, at most about 164 k floats, and its cost is the launch (not
+ * timed).  tensors[i] / counts[i], i < n, 1 <= n <= 32: read only, any 4-byte boundary, any count >= 0 (a pointer may be NULL where
+ * its count is 0).  The sum of the squares of every element is taken in DOUBLE, each square and each addition, in an order that the
+ * segment list alone fixes: thread t walks the segments in order and takes of each the element t of the head (the floats in front of
+ * the first 16-byte boundary), the 16-byte groups t, t + 1024, ... in ascending address and the element t of the tail; a wavefront
+ * adds its lanes x[l] + x[l ^ 32], then ^ 16 .. ^ 1, and the sixteen wavefronts are added in ascending order.  No atomics: the same
+ * input gives the same bits on every call.  out2 (device, two floats):
+ *   out2[0] = (float)sqrt(sum)
+ *   out2[1] = the coefficient as torch forms it, in float32: c = (1 / (out2[0] + 1e-6f)) * max_norm - torch evaluates its
+ *             `max_norm / (total_norm + 1e-6)` as reciprocal() * max_norm, two roundings - then c where c < 1, 1 where c >= 1 and c
+ *             itself where it is NaN (torch.clamp(max=1) keeps a NaN).  max_norm = +INFINITY measures only: out2[1] = 1 whatever
+ *             the norm.  A NaN element gives (NaN, NaN), an infinite one (+inf, 0).
+ * SKYJO_E_INVALID (nothing is launched, out2 is untouched): a null argument, n outside 1 .. 32, a negative count, a NULL tensor with
+ * a count > 0, a tensor or out2 that is not 4-byte aligned, max_norm NaN or <= 0.
+ *
+ * skyjo_vec_mlp_adam_step_clipped: skyjo_vec_mlp_adam_step - the same kernel, the same arguments and checks - with one change: every
+ * thread reads *coef_device (device, one float32: out2 + 1 of a skyjo_vec_grad_norm queued before it on the same stream) and the rule
+ * takes g * *coef_device, ONE rounded float32 multiply, wherever it reads g.  The gradients themselves are not rewritten.  With a
+ * coefficient of exactly 1 the result carries the bits of skyjo_vec_mlp_adam_step; a NaN coefficient reaches every parameter, as
+ * torch's does (no step is skipped: the host owns the step count).  SKYJO_E_INVALID besides the unclipped step's: coef_device NULL or
+ * not 4-byte aligned.
+ *
  * Ordering is the stream's: a net launch or rollout queued on the same stream afterwards sees the new weights.  A launch on ANOTHER
  * stream that still reads the net is the caller's race.
  *
@@ -423,6 +447,9 @@ int skyjo_vec_mlp_update(skyjo_vec_mlp *m, const float *w1, const float *b1, con
 int64_t skyjo_vec_mlp_adam_state_bytes(const skyjo_vec_mlp *m); /* 0 for NULL */
 int skyjo_vec_mlp_adam_step(skyjo_vec_mlp *m, float *const params[6], const float *const grads[6], void *state, int64_t state_bytes,
                             float lr, float beta1, float beta2, float eps, int64_t step, void *stream);
+int skyjo_vec_grad_norm(const float *const tensors[], const int64_t counts[], int32_t n, float max_norm, float *out2, void *stream);
+int skyjo_vec_mlp_adam_step_clipped(skyjo_vec_mlp *m, float *const params[6], const float *const grads[6], void *state, int64_t state_bytes,
+                                    float lr, float beta1, float beta2, float eps, int64_t step, const float *coef_device, void *stream);
 int64_t skyjo_vec_mlp_packed_bytes(const skyjo_vec_mlp *m); /* 0 for NULL */
 int skyjo_vec_mlp_export(const skyjo_vec_mlp *m, void *dst_device, int64_t bytes, void *stream);
 

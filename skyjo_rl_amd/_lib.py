@@ -113,6 +113,8 @@ SIGNATURES = {
     "skyjo_vec_mlp_update": (C.c_int, [VP, VP, VP, VP, VP, VP, VP, VP]),
     "skyjo_vec_mlp_adam_state_bytes": (I64, [VP]),
     "skyjo_vec_mlp_adam_step": (C.c_int, [VP, VP, VP, VP, I64, C.c_float, C.c_float, C.c_float, C.c_float, I64, VP]),
+    "skyjo_vec_grad_norm": (C.c_int, [VP, VP, I32, C.c_float, VP, VP]),
+    "skyjo_vec_mlp_adam_step_clipped": (C.c_int, [VP, VP, VP, VP, I64, C.c_float, C.c_float, C.c_float, C.c_float, I64, VP, VP]),
     "skyjo_vec_mlp_packed_bytes": (I64, [VP]),
     "skyjo_vec_mlp_export": (C.c_int, [VP, VP, I64, VP]),
     "skyjo_vec_step_collect":(C.c_int, [VP, VP, VP, VP, VP, VP]),

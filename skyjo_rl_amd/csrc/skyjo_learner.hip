@@ -1,6 +1,6 @@
 // skyjo_learner.hip - the packed nets' handles and the learner behind the extern "C" boundary of include/skyjo_vec.h: skyjo_vec_mlp_*,
-// skyjo_vec_rollout_targets / _select / _gather / _gather_logits, skyjo_vec_ppo_loss / _kl, skyjo_vec_mlp_train_*, skyjo_vec_arena_* and skyjo_vec_episode_stats,
-// with their kernels (skyjo_update.h, skyjo_targets.h, skyjo_batches.h, skyjo_loss.h, skyjo_train.h, skyjo_arena.h; what they share: skyjo_learner_util.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
+// skyjo_vec_rollout_targets / _select / _gather / _gather_logits, skyjo_vec_ppo_loss / _kl, skyjo_vec_mlp_train_*, skyjo_vec_grad_norm, skyjo_vec_arena_* and skyjo_vec_episode_stats,
+// with their kernels (skyjo_update.h, skyjo_clip.h, skyjo_targets.h, skyjo_batches.h, skyjo_loss.h, skyjo_train.h, skyjo_arena.h; what they share: skyjo_learner_util.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
 // (skyjo_capi.hip, skyjo_device.h and its parts), and of an engine it sees what skyjo_host.h shows - the record layout, B, G, game_id0,
 // the device and the select scratch.  gfx950 only, no CPU path.
 #include <hip/hip_runtime.h>
@@ -12,6 +12,7 @@
 #include "skyjo_host.h"
 #include "skyjo_learner_util.h"
 #include "skyjo_update.h"
+#include "skyjo_clip.h"
 #include "skyjo_targets.h"
 #include "skyjo_batches.h"
 #include "skyjo_loss.h"
@@ -106,23 +107,26 @@ int64_t skyjo_vec_mlp_adam_state_bytes(const skyjo_vec_mlp *m) {
   return m ? (int64_t)(2 * sku_state_half(m->obs_dim, m->out_dim) * sizeof(float)) : 0;
 }
 
-int skyjo_vec_mlp_adam_step(skyjo_vec_mlp *m, float *const params[6], const float *const grads[6], void *state, int64_t state_bytes,
-                            float lr, float beta1, float beta2, float eps, int64_t step, void *stream) {
+// both Adam entries: the checks, the scalars and the launch.  coef: the clipped entry's coefficient on the device, or null
+static int adam_step(const char *who, skyjo_vec_mlp *m, float *const params[6], const float *const grads[6], void *state, int64_t state_bytes,
+                     float lr, float beta1, float beta2, float eps, int64_t step, const float *coef, void *stream) {
+  const std::string name(who);
   SkUpdArgs a{};
-  if (!m || !params || !grads || !state || !mlp_update_args(m, params, a)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: null argument");
+  if (!m || !params || !grads || !state || !mlp_update_args(m, params, a)) return fail(SKYJO_E_INVALID, name + ": null argument");
   for (int i = 0; i < SKU_TENSORS; i++) {
-    if (!grads[i]) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: null gradient");
+    if (!grads[i]) return fail(SKYJO_E_INVALID, name + ": null gradient");
     a.g[i] = grads[i];
     a.off[i] = sku_tensor_offset(i, m->obs_dim, m->out_dim);
   }
   if (state_bytes < skyjo_vec_mlp_adam_state_bytes(m))
-    return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: state_bytes is less than skyjo_vec_mlp_adam_state_bytes");
-  if (step < 1) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: step counts from 1");
-  if (!std::isfinite(lr)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: lr must be finite");
-  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: beta1 and beta2 must lie in [0, 1)");
-  if (!(std::isfinite(eps) && eps >= 0.f)) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: eps must be finite and not negative");
+    return fail(SKYJO_E_INVALID, name + ": state_bytes is less than skyjo_vec_mlp_adam_state_bytes");
+  if (step < 1) return fail(SKYJO_E_INVALID, name + ": step counts from 1");
+  if (!std::isfinite(lr)) return fail(SKYJO_E_INVALID, name + ": lr must be finite");
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return fail(SKYJO_E_INVALID, name + ": beta1 and beta2 must lie in [0, 1)");
+  if (!(std::isfinite(eps) && eps >= 0.f)) return fail(SKYJO_E_INVALID, name + ": eps must be finite and not negative");
   if (!aligned16(state) || !aligned16(params[2]) || !aligned16(params[4]) || !aligned16(grads[2]) || !aligned16(grads[4]))
-    return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_adam_step: state, w2, w3 and their gradients must be 16-byte aligned");
+    return fail(SKYJO_E_INVALID, name + ": state, w2, w3 and their gradients must be 16-byte aligned");
+  a.coef = coef;
   a.m = (float *)state, a.v = a.m + sku_state_half(m->obs_dim, m->out_dim);
   // torch.optim.Adam's scalars, in double from the float32 hyper-parameters and the step, rounded to float32 once
   const double b1 = (double)beta1, b2 = (double)beta2, t = (double)step;
@@ -132,6 +136,39 @@ int skyjo_vec_mlp_adam_step(skyjo_vec_mlp *m, float *const params[6], const floa
   a.eps = eps;
   DevGuard guard_(m->device_id);
   hipLaunchKernelGGL(k_mlp_update<true>, dim3(SKU_BLOCKS), dim3(SKU_THREADS), 0, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+int skyjo_vec_mlp_adam_step(skyjo_vec_mlp *m, float *const params[6], const float *const grads[6], void *state, int64_t state_bytes,
+                            float lr, float beta1, float beta2, float eps, int64_t step, void *stream) {
+  return adam_step("skyjo_vec_mlp_adam_step", m, params, grads, state, state_bytes, lr, beta1, beta2, eps, step, nullptr, stream);
+}
+
+int skyjo_vec_mlp_adam_step_clipped(skyjo_vec_mlp *m, float *const params[6], const float *const grads[6], void *state, int64_t state_bytes,
+                                    float lr, float beta1, float beta2, float eps, int64_t step, const float *coef_device, void *stream) {
+  static const char *who = "skyjo_vec_mlp_adam_step_clipped";
+  if (!coef_device) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
+  if ((uintptr_t)coef_device & 3) return fail(SKYJO_E_INVALID, std::string(who) + ": coef_device is not aligned to its element size");
+  return adam_step(who, m, params, grads, state, state_bytes, lr, beta1, beta2, eps, step, coef_device, stream);
+}
+
+// ---- the global L2 norm of a list of tensors and torch's clipping coefficient (include/skyjo_vec.h: skyjo_vec_grad_norm; skyjo_clip.h) ----
+int skyjo_vec_grad_norm(const float *const tensors[], const int64_t counts[], int32_t n, float max_norm, float *out2, void *stream) {
+  static const char *who = "skyjo_vec_grad_norm";
+  if (!tensors || !counts || !out2) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
+  if (n < 1 || n > SKC_MAX_SEGMENTS) return fail(SKYJO_E_INVALID, std::string(who) + ": n must lie in 1 .. 32");
+  if (!(max_norm > 0.f)) return fail(SKYJO_E_INVALID, std::string(who) + ": max_norm must be greater than 0 (+inf: measure only)");
+  if ((uintptr_t)out2 & 3) return fail(SKYJO_E_INVALID, std::string(who) + ": out2 is not aligned to its element size");
+  SkNormArgs a{};
+  for (int i = 0; i < n; i++) {
+    if (counts[i] < 0) return fail(SKYJO_E_INVALID, std::string(who) + ": a count is negative");
+    if (!tensors[i] && counts[i] > 0) return fail(SKYJO_E_INVALID, std::string(who) + ": a null tensor with a count greater than 0");
+    if ((uintptr_t)tensors[i] & 3) return fail(SKYJO_E_INVALID, std::string(who) + ": a tensor is not aligned to its element size");
+    a.ptr[i] = tensors[i], a.count[i] = (long long)counts[i];
+  }
+  a.n = n, a.max_norm = max_norm, a.out = out2;
+  hipLaunchKernelGGL(k_grad_norm, dim3(1), dim3(SKC_THREADS), 0, (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return SKYJO_OK;
 }

@@ -1,7 +1,7 @@
 // skyjo_update.h - included from skyjo_learner.hip after skyjo_policy.h (it uses SKP_*).  The packed net's layout, stated once, and the
 // kernel that writes an existing skyjo_vec_mlp's blob in place from device memory: skyjo_vec_mlp_update (repack) and
-// skyjo_vec_mlp_adam_step (torch.optim.Adam's rule in front of the pack).  include/skyjo_vec.h and DESIGN.md 4 have the definition;
-// tests/mlp_pack_ref.py restates the layout.
+// skyjo_vec_mlp_adam_step / _adam_step_clipped (torch.optim.Adam's rule in front of the pack, on g or on g times a coefficient read
+// from the device).  include/skyjo_vec.h and DESIGN.md 4 have the definition; tests/mlp_pack_ref.py restates the layout.
 //
 // (a) There is one packer: k_mlp_update.  skyjo_vec_mlp_create stages its host arrays on the device and runs it too, so the skp_* packing
 //     helpers are device code only.  The unit is compiled with -ffp-contract=off, which makes the kernel's arithmetic the reference's
@@ -125,6 +125,9 @@ struct SkUpdArgs {
   int obs_dim, out_dim, split;
   // torch.optim.Adam's scalars, rounded to float32 once on the host: 1 - beta1, beta2, 1 - beta2, lr / (1 - beta1^t), sqrt(1 - beta2^t), eps
   float w1, beta2, w2, step_size, bc2_sqrt, eps;
+  // ADAM only, skyjo_vec_mlp_adam_step_clipped: the clipping coefficient on the device (skyjo_clip.h) - the rule takes g * *coef, one
+  // rounded float32 multiply, for g.  Null: g as it is, skyjo_vec_mlp_adam_step bit for bit
+  const float *coef;
 };
 
 // both views of a blob, from its base: the net kernels' (read only; no low halves in bf16 mode) and k_mlp_update's
@@ -149,13 +152,17 @@ __device__ inline float sku_adam(const SkUpdArgs &a, float p, float g, float &m,
   return p + (-a.step_size * m) / denom;
 }
 
+// the gradient the rule takes: g, or with a coefficient g * coef
+__device__ inline float sku_grad(const SkUpdArgs &a, float g, float coef) { return a.coef ? g * coef : g; }
+
+// coef: *a.coef, read once per thread (k_mlp_update); counts with a.coef only
 template <bool ADAM>
-__device__ inline float sku_elem(const SkUpdArgs &a, int tensor, size_t i) {
+__device__ inline float sku_elem(const SkUpdArgs &a, int tensor, size_t i, float coef) {
   float p = a.p[tensor][i];
   if (ADAM) {
     const size_t s = a.off[tensor] + i;
     float m = a.m[s], v = a.v[s];
-    p = sku_adam(a, p, a.g[tensor][i], m, v);
+    p = sku_adam(a, p, sku_grad(a, a.g[tensor][i], coef), m, v);
     a.p[tensor][i] = p, a.m[s] = m, a.v[s] = v;
   }
   return p;
@@ -163,7 +170,7 @@ __device__ inline float sku_elem(const SkUpdArgs &a, int tensor, size_t i) {
 
 // four consecutive elements of w2 / w3 (i a multiple of 4: 16-byte accesses)
 template <bool ADAM>
-__device__ inline void sku_elem4(const SkUpdArgs &a, int tensor, size_t i, float *out) {
+__device__ inline void sku_elem4(const SkUpdArgs &a, int tensor, size_t i, float *out, float coef) {
   const float4 p = *(const float4 *)(a.p[tensor] + i);
   out[0] = p.x, out[1] = p.y, out[2] = p.z, out[3] = p.w;
   if (ADAM) {
@@ -171,7 +178,7 @@ __device__ inline void sku_elem4(const SkUpdArgs &a, int tensor, size_t i, float
     const float4 g = *(const float4 *)(a.g[tensor] + i), m4 = *(const float4 *)(a.m + s), v4 = *(const float4 *)(a.v + s);
     float gg[4] = {g.x, g.y, g.z, g.w}, m[4] = {m4.x, m4.y, m4.z, m4.w}, v[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
-    for (int j = 0; j < 4; j++) out[j] = sku_adam(a, out[j], gg[j], m[j], v[j]);
+    for (int j = 0; j < 4; j++) out[j] = sku_adam(a, out[j], sku_grad(a, gg[j], coef), m[j], v[j]);
     *(float4 *)(a.p[tensor] + i) = make_float4(out[0], out[1], out[2], out[3]);
     *(float4 *)(a.m + s) = make_float4(m[0], m[1], m[2], m[3]);
     *(float4 *)(a.v + s) = make_float4(v[0], v[1], v[2], v[3]);
@@ -201,11 +208,12 @@ __global__ __launch_bounds__(SKU_THREADS) void k_mlp_update(SkUpdArgs a) {
   const int t = threadIdx.x, l = t & 63, ks = t >> 6, hh = l >> 5;
   const bool split = a.split != 0;
   const int k0 = skp_acc_k(ks, hh, 0);  // the fragment's k are k0 .. k0 + 3 and k0 + 8 .. k0 + 11
+  const float coef = ADAM && a.coef ? *a.coef : 1.f;
   if (blockIdx.x < 8) {
     const int u = blockIdx.x, m = skp_row(u, l);
     float x[8];
-    sku_elem4<ADAM>(a, 2, (size_t)m * SKP_HIDDEN + k0, x);
-    sku_elem4<ADAM>(a, 2, (size_t)m * SKP_HIDDEN + k0 + 8, x + 4);
+    sku_elem4<ADAM>(a, 2, (size_t)m * SKP_HIDDEN + k0, x, coef);
+    sku_elem4<ADAM>(a, 2, (size_t)m * SKP_HIDDEN + k0 + 8, x + 4, coef);
 #pragma unroll
     for (int j = 0; j < 8; j++) x[j] = skp_scaled(x[j]);
     sku_store_frag(x, split, true, a.f2, a.g2, skp_w2_frag(u, ks, l));
@@ -213,25 +221,25 @@ __global__ __launch_bounds__(SKU_THREADS) void k_mlp_update(SkUpdArgs a) {
 #pragma unroll
       for (int j = 0; j < 8; j++) {
         const int k = skp_w1_k(ks, hh, j);
-        x[j] = skp_scaled(k < a.obs_dim ? sku_elem<ADAM>(a, 0, (size_t)m * a.obs_dim + k) : (k == SKP_IN - 1 ? sku_elem<ADAM>(a, 1, m) : 0.f));
+        x[j] = skp_scaled(k < a.obs_dim ? sku_elem<ADAM>(a, 0, (size_t)m * a.obs_dim + k, coef) : (k == SKP_IN - 1 ? sku_elem<ADAM>(a, 1, m, coef) : 0.f));
       }
       sku_store_frag(x, split, false, a.f1, a.g1, skp_w1_frag(u, ks, l));
     }
     __syncthreads();  // the workgroup's rows of w2 are written: bf16 mode sums them
     if (t < 32) {
       const int row = 32 * u + t;
-      a.c2[row] = skp_bias_sum(sku_elem<ADAM>(a, 3, row), a.p[2] + (size_t)row * SKP_HIDDEN, true, split);
+      a.c2[row] = skp_bias_sum(sku_elem<ADAM>(a, 3, row, coef), a.p[2] + (size_t)row * SKP_HIDDEN, true, split);
     }
   } else {
     const int m = l & 31;
     float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (m < a.out_dim) {
-      sku_elem4<ADAM>(a, 4, (size_t)m * SKP_HIDDEN + k0, x);
-      sku_elem4<ADAM>(a, 4, (size_t)m * SKP_HIDDEN + k0 + 8, x + 4);
+      sku_elem4<ADAM>(a, 4, (size_t)m * SKP_HIDDEN + k0, x, coef);
+      sku_elem4<ADAM>(a, 4, (size_t)m * SKP_HIDDEN + k0 + 8, x + 4, coef);
     }
     sku_store_frag(x, split, true, a.f3, a.g3, skp_w3_frag(ks, l));
     __syncthreads();
-    if (t < 32) rowb[t] = t < a.out_dim ? skp_bias_sum(sku_elem<ADAM>(a, 5, t), a.p[4] + (size_t)t * SKP_HIDDEN, false, split) : 0.f;
+    if (t < 32) rowb[t] = t < a.out_dim ? skp_bias_sum(sku_elem<ADAM>(a, 5, t, coef), a.p[4] + (size_t)t * SKP_HIDDEN, false, split) : 0.f;
     __syncthreads();
     if (t < 256) {  // lane t / 4, registers 4 q .. 4 q + 3: the rows 8 q + 4 hh + 0 .. 3
       const int lane = t >> 2, q = t & 3, r0 = skp_b3_row(4 * q, lane >> 5);

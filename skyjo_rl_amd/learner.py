@@ -3,8 +3,9 @@ and returns the PPO loss, its statistics and the gradients with respect to both 
 reduction (``skyjo_vec_ppo_loss``, csrc/skyjo_loss.h) instead of the chain of small torch expressions and their autograd twins that
 otherwise stands between the model and ``optimizer.step()``.  ``PPOLoss`` wraps it as a ``torch.autograd.Function``.  ``NativeAdam`` is the
 step itself: Adam fused with the re-pack of the updated weights into the ``FusedNet``s' MFMA fragments, in place (``skyjo_vec_mlp_adam_step``,
-csrc/skyjo_update.h) - the rollout that follows needs no new nets.  ``NativeBranch`` is what remains in between: one branch's forward,
-which keeps its activations, and its backward on the float32 master parameters (``skyjo_vec_mlp_train_forward`` / ``_backward``,
+csrc/skyjo_update.h) - the rollout that follows needs no new nets - and with ``max_grad_norm`` RLlib's ``grad_clip`` in front of it: ``grad_norm``
+(``skyjo_vec_grad_norm``, csrc/skyjo_clip.h) takes the global norm of both branches' gradients and the step reads the coefficient from the
+device.  ``NativeBranch`` is what remains in between: one branch's forward, which keeps its activations, and its backward on the float32 master parameters (``skyjo_vec_mlp_train_forward`` / ``_backward``,
 csrc/skyjo_train.h: the exact float32 matrix instruction, no autograd graph, no allocation per step).
 
 The definition (include/skyjo_vec.h has it in full): the masked softmax of ``action_mask_model.py:58-74`` - logits plus
@@ -211,6 +212,50 @@ class PPOLossKL(torch.autograd.Function):
     backward = staticmethod(_head_backward)
 
 
+MAX_NORM_SEGMENTS = 32  # SKC_MAX_SEGMENTS of csrc/skyjo_clip.h: the tensors of one ``grad_norm``
+
+
+def _max_norm(name, max_norm):
+    """``max_norm`` as the float the ABI takes: None - +inf, measure only; otherwise its float32 value must be greater than 0."""
+    if max_norm is None:
+        return math.inf
+    if isinstance(max_norm, bool) or not isinstance(max_norm, (int, float)):
+        raise ValueError(name + " must be None or a number")
+    x = float(max_norm)
+    if not C.c_float(x).value > 0.0:  # (NaN, <= 0, or so small that it is 0 as a float32)
+        raise ValueError(name + " must be greater than 0 as a float32, and not NaN")
+    return x
+
+
+@torch.no_grad()
+def grad_norm(tensors, max_norm=None, out=None):
+    """The global L2 norm of ``tensors`` - a list of 1 to 32 contiguous float32 tensors on one GPU, of any shapes - and the coefficient
+    ``torch.nn.utils.clip_grad_norm_(.., max_norm)`` would scale them by, in ONE native launch on torch's current stream
+    (``skyjo_vec_grad_norm``, csrc/skyjo_clip.h; not timed: a single workgroup, its cost is the launch).  Returns a float32 ``[2]``
+    tensor on that GPU, ``(norm, coef)``: the sum of squares is accumulated in double in a fixed order - the same input gives the same
+    bits on every call - and rounded once after the root; ``coef`` is torch's float32 ``clamp(max_norm / (norm + 1e-6), max=1)`` bit for
+    bit (torch evaluates the quotient as ``reciprocal() * max_norm``), NaN where the norm is.  ``max_norm`` None (or inf): measure
+    only, ``coef`` is 1.  Nothing is read back: no host synchronisation.  The tensors are not changed.  ``out``: a contiguous float32
+    ``[2]`` tensor on the same GPU to write instead of a new one."""
+    if not isinstance(tensors, (list, tuple)) or not 1 <= len(tensors) <= MAX_NORM_SEGMENTS:
+        raise ValueError(f"tensors must be a list of 1 to {MAX_NORM_SEGMENTS} tensors")
+    if not isinstance(tensors[0], torch.Tensor) or tensors[0].device.type != "cuda":
+        raise ValueError("grad_norm runs on the GPU: tensors[0] is not a tensor there")
+    dev = tensors[0].device
+    for i, t in enumerate(tensors):
+        _column(f"tensors[{i}]", t, torch.float32, tuple(t.shape) if isinstance(t, torch.Tensor) else (), dev)
+    x = _max_norm("max_norm", max_norm)
+    if out is None:
+        out = torch.empty((2,), dtype=torch.float32, device=dev)
+    else:
+        _column("out", out, torch.float32, (2,), dev)
+    n = len(tensors)
+    pp, cc = (C.c_void_p * n)(*[t.data_ptr() for t in tensors]), (C.c_int64 * n)(*[t.numel() for t in tensors])
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().skyjo_vec_grad_norm(pp, cc, n, x, out.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return out
+
+
 class NativeAdam:
     """``torch.optim.Adam`` (no amsgrad, no weight decay) for ``model``'s two branches, fused with the re-pack of their ``FusedNet``s:
     ``step()`` is one ``skyjo_vec_mlp_adam_step`` per branch - two kernel launches on torch's current stream, nothing else.  Each
@@ -221,11 +266,23 @@ class NativeAdam:
     Duck-typed to what ``examples/ppo.py:ppo_update`` calls on its ``optimizer`` (``zero_grad``, ``step``); not a
     ``torch.optim.Optimizer``.  ``lr`` is a plain attribute and may be set between steps.  ``lr``, ``betas`` and ``eps`` reach the
     kernel as float32 (the ABI's type): the bias corrections are computed from the float32 values of the betas.  ``state`` maps a
-    parameter to its ``exp_avg`` / ``exp_avg_sq`` views, as ``torch.optim.Adam.state`` does."""
+    parameter to its ``exp_avg`` / ``exp_avg_sq`` views, as ``torch.optim.Adam.state`` does.
 
-    def __init__(self, model, policy_net, value_net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    ``max_grad_norm``: None - exactly the above, and ``grad_stats`` is None.  A number - the gradients are clipped by their global L2
+    norm as ``torch.nn.utils.clip_grad_norm_`` over all TWELVE tensors of the two branches clips them (RLlib's ``grad_clip``: one norm
+    per policy, not one per branch), without leaving the native path: ``step()`` is then three launches - ``grad_norm`` over the twelve
+    ``.grad``s into ``grad_stats``, a float32 ``[2]`` device tensor ``(norm before clipping, coefficient)`` allocated here, once, and one
+    ``skyjo_vec_mlp_adam_step_clipped`` per branch, which reads the coefficient from there and takes ``g * coef`` for ``g``; the
+    ``.grad``s themselves are not rewritten.  Still no allocation and no synchronisation; ``grad_stats`` holds the last step's pair
+    (read it when you read your other statistics).  inf: measure only, the coefficient is 1 and the step carries the bits of the
+    unclipped one.  A non-finite norm is not caught: the NaN reaches the parameters, as it does with torch.  Like ``lr`` a plain
+    attribute that may be set between steps; it is checked in ``step()`` before the first launch.  The three launches were not timed."""
+
+    def __init__(self, model, policy_net, value_net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None):
         self._L = _lib.load()
         self.lr, self.betas, self.eps = lr, (float(betas[0]), float(betas[1])), float(eps)
+        _max_norm("max_grad_norm", max_grad_norm)
+        self.max_grad_norm = max_grad_norm
         self.steps = 0
         self.state = {}
         self._branches = []
@@ -240,6 +297,13 @@ class NativeAdam:
                 at += p.numel()
             pp = (C.c_void_p * 6)(*[p.data_ptr() for p in params])
             self._branches.append((net, params, buf, pp))
+        self._stats = torch.zeros((2,), dtype=torch.float32, device=self._branches[0][2].device)
+        self._counts = (C.c_int64 * 12)(*[p.numel() for _, params, _, _ in self._branches for p in params])
+
+    @property
+    def grad_stats(self):
+        """float32 ``[2]`` on the device, ``(norm, coefficient)`` of the last ``step()``; None while ``max_grad_norm`` is None."""
+        return None if self.max_grad_norm is None else self._stats
 
     def zero_grad(self, set_to_none=True):
         for _, params, _, _ in self._branches:
@@ -254,6 +318,10 @@ class NativeAdam:
     @torch.no_grad()
     def step(self):
         calls = []
+        clip = self.max_grad_norm is not None
+        max_norm = _max_norm("max_grad_norm", self.max_grad_norm)
+        if clip and any(buf.device != self._stats.device for _, _, buf, _ in self._branches):
+            raise ValueError("max_grad_norm needs both branches on one GPU: the norm is one launch over their twelve gradients")
         for net, params, buf, pp in self._branches:  # every check before the first launch: both branches step, or neither
             if not net._h:
                 raise ValueError("a FusedNet of this optimizer is closed")
@@ -262,10 +330,19 @@ class NativeAdam:
                     raise ValueError("a parameter has no gradient (.grad is None): NativeAdam steps every parameter of both branches")
                 _column("a parameter's .grad", p.grad, torch.float32, tuple(p.shape), p.device)
             calls.append((net, buf, pp, (C.c_void_p * 6)(*[p.grad.data_ptr() for p in params])))
+        if clip:
+            twelve = (C.c_void_p * 12)(*[g for _, _, _, gg in calls for g in gg])
+            with torch.cuda.device(self._stats.device):
+                _lib.check(self._L.skyjo_vec_grad_norm(twelve, self._counts, 12, max_norm, self._stats.data_ptr(),
+                                                       torch.cuda.current_stream().cuda_stream))
         for net, buf, pp, gg in calls:
+            hyper = (buf.data_ptr(), buf.numel() * 4, float(self.lr), self.betas[0], self.betas[1], self.eps, self.steps + 1)
             with torch.cuda.device(buf.device):
-                _lib.check(self._L.skyjo_vec_mlp_adam_step(net._h, pp, gg, buf.data_ptr(), buf.numel() * 4, float(self.lr), self.betas[0],
-                                                           self.betas[1], self.eps, self.steps + 1, torch.cuda.current_stream().cuda_stream))
+                stream = torch.cuda.current_stream().cuda_stream
+                if clip:
+                    _lib.check(self._L.skyjo_vec_mlp_adam_step_clipped(net._h, pp, gg, *hyper, self._stats.data_ptr() + 4, stream))
+                else:
+                    _lib.check(self._L.skyjo_vec_mlp_adam_step(net._h, pp, gg, *hyper, stream))
         self.steps += 1
 
 
