@@ -14,8 +14,9 @@ import torch
 
 from skyjo_rl_amd._lib import TGT_HAS_TARGET
 from skyjo_rl_amd.action_mask_model import FLOAT_MIN, FusedNet
-from skyjo_rl_amd.learner import STATS, STATS_KL, KLCoeff, NativeAdam, NativeBranch, PPOLossBuffers, PPOLossKLBuffers, ppo_loss, ppo_loss_kl
-from skyjo_rl_amd.rollout import Minibatch, behaviour_logits, compute_targets, minibatches, select_rows
+from skyjo_rl_amd.learner import (STATS, STATS_KL, UPDATE_STATS, KLCoeff, NativeAdam, NativeBranch, NativeUpdate, PPOLossBuffers, PPOLossKLBuffers, ppo_loss,
+                                  ppo_loss_kl)
+from skyjo_rl_amd.rollout import Minibatch, behaviour_logits, compute_targets, epoch_order, minibatches, select_rows
 
 
 @torch.no_grad()
@@ -96,15 +97,56 @@ def _torch_batches(buf, minibatch, seed, gae):
     return epoch, int(idx.numel())
 
 
-def _native_batches(buf, minibatch, seed, gae, seats, behaviour):
+def _native_batches(buf, minibatch, seed, gae, seats, behaviour, shuffle):
     """The native batch source: ``rollout.minibatches`` on the buffer as it lies - with ``behaviour``, ``(minibatch, old_logits)``.
-    Returns ``(epoch, transitions)`` as ``_torch_batches`` does."""
+    ``shuffle``: "torch" - a ``randperm`` per epoch from one generator seeded with ``seed``; "native" - ``rollout.epoch_order(sel, seed,
+    ep)``, ``ep`` counting the epochs of the call from 0, into one index tensor that every epoch refills (its fault word stays unread: this
+    loop reads once per epoch, and that read is the statistics').  Returns ``(epoch, transitions)`` as ``_torch_batches`` does."""
     compute_targets(buf, gamma=gae[0], lam=gae[1])
     sel = select_rows(buf, TGT_HAS_TARGET, seats=seats)
     norm = (sel.mean, max(sel.std, 1e-6))
-    gen = torch.Generator(device=buf.actions.device).manual_seed(seed)
     kw = {"behaviour": True} if behaviour else {}
+    if shuffle == "native":
+        order, ep = torch.empty((sel.count,), dtype=torch.int64, device=buf.actions.device), [0]
+
+        def epoch():
+            ep[0] += 1
+            return minibatches(buf, minibatch, normalize=norm, selection=sel, order=epoch_order(sel, seed, ep[0] - 1, out=order)[0], **kw)
+
+        return epoch, sel.count
+    gen = torch.Generator(device=buf.actions.device).manual_seed(seed)
     return (lambda: minibatches(buf, minibatch, generator=gen, normalize=norm, selection=sel, **kw)), sel.count
+
+
+def _native_update(model, buf, optimizer, epochs, minibatch, seed, gae, seats, kl, coeff, grad_clip, head):
+    """``ppo_update(native_update=True)``: the selection, ``learner.NativeUpdate`` on the optimizer's nets and ONE read - the epochs'
+    statistics with the fault word - turned into the result ``_epochs`` returns, by its host arithmetic."""
+    compute_targets(buf, gamma=gae[0], lam=gae[1])
+    sel = select_rows(buf, TGT_HAS_TARGET, seats=seats)
+    (policy_net, _, _, _), (value_net, _, _, _) = optimizer._branches
+    update = NativeUpdate(buf._env, model, policy_net, value_net, optimizer, sel.count, minibatch, epochs, kl=kl is not None)
+    # (without grad_clip the optimizer's own max_grad_norm holds, as in its step(); the statistics report the clipping grad_clip asks for)
+    stats, fault = update.run(buf, sel, seed=seed, kl_coeff=None if kl is None else coeff,
+                              grad_clip=optimizer.max_grad_norm if grad_clip is None else grad_clip, **head)
+    host = torch.cat([stats.reshape(-1), fault.to(torch.float64)]).tolist()  # the call's one read
+    names = STATS if kl is None else STATS_KL
+    per_epoch = []
+    total_kl, total_rows = 0.0, 0
+    for ep in range(epochs):
+        row = dict(zip(UPDATE_STATS, host[ep * len(UPDATE_STATS):(ep + 1) * len(UPDATE_STATS)]))
+        per_epoch.append({k: row[k] for k in _REPORTED if k in names})
+        if grad_clip is not None and sel.count:
+            per_epoch[-1].update((k, row[k]) for k in _CLIP_STATS)
+        if kl is not None:
+            total_kl += row["action_kl"] * sel.count
+            total_rows += sel.count
+    result = {"first": per_epoch[0], "last": per_epoch[-1], "transitions": sel.count}
+    if kl is not None:
+        mean_kl = total_kl / max(total_rows, 1)
+        result.update(mean_action_kl=mean_kl, kl_coeff=kl.update(mean_kl) if isinstance(kl, KLCoeff) and total_rows else float(kl))
+    if host[-1] != 0.0:
+        raise RuntimeError("skyjo_vec_ppo_update: %d positions of the epochs' orders hit the walk cap (their rows entered as zeros)" % int(host[-1]))
+    return result
 
 
 def _torch_loss(model, mb, clip, vf_coef):
@@ -165,7 +207,8 @@ def _epochs(epochs, batches, names, evaluate, read, step, device, transitions, k
 
 
 def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_coef=1.0, seed=0, gae=None, native_batches=False,
-               native_loss=False, ent_coef=0.0, vf_clip=None, native_nets=False, seats=None, kl=None, behaviour_net=None, grad_clip=None):
+               native_loss=False, ent_coef=0.0, vf_clip=None, native_nets=False, seats=None, kl=None, behaviour_net=None, grad_clip=None,
+               shuffle="torch", native_update=False):
     """Clipped-surrogate PPO epochs over the buffer (RLlib defaults: clip_param 0.3, vf_loss_coeff 1.0).  Returns the mean
     losses of the first and the last epoch.  ``gae``: None - Monte-Carlo returns of the episodes that ended inside the buffer
     (``compute_returns``); (gamma, lambda) - advantages, value targets and the row mask of ``rollout.compute_targets`` (one
@@ -190,7 +233,19 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
     torch optimizer through ``torch.nn.utils.clip_grad_norm_`` between the backward and its step.  The epoch statistics gain
     ``grad_norm`` - the mean over the epoch's steps of the norm before clipping - and ``grad_clipped``, the share of steps whose
     coefficient was below 1; both are summed on the device and come with the epoch's read.  None: no clipping, every path and every
-    result as without the keyword."""
+    result as without the keyword.  ``shuffle`` ("native" needs ``native_batches``): "torch" - an epoch's order is a ``torch.randperm``
+    from a generator seeded with ``seed``; "native" - ``rollout.epoch_order(sel, seed, ep)``, ``ep`` counted from 0 inside the call: one
+    native launch pair per epoch, no generator, no fancy-index allocation.  ``native_update`` (needs ``native_nets``, ``shuffle="native"``
+    and a ``learner.NativeAdam``): the whole update is ONE native call (``learner.NativeUpdate``, ``skyjo_vec_ppo_update``) that queues the
+    launches the loop below would make, in its order - parameters, Adam state, nets and every number of the result carry the bits of
+    ``native_update=False`` - and the statistics of all epochs are read once, at the end; a non-zero fault word of the shuffles raises
+    ``RuntimeError`` after that read.  The parameters' ``.grad`` are not touched on this path."""
+    if shuffle not in ("torch", "native"):
+        raise ValueError('shuffle must be "torch" or "native"')
+    if shuffle == "native" and not native_batches:
+        raise ValueError('shuffle="native" needs native_batches=True')
+    if native_update and not (native_nets and shuffle == "native" and isinstance(optimizer, NativeAdam)):
+        raise ValueError('native_update=True needs native_nets=True, shuffle="native" and a learner.NativeAdam as optimizer')
     if grad_clip is not None:
         if isinstance(grad_clip, bool) or not isinstance(grad_clip, (int, float)) or not (math.isfinite(grad_clip) and grad_clip > 0):
             raise ValueError("grad_clip must be None or a finite number greater than 0")
@@ -222,7 +277,10 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
     step = optimizer.step if grad_clip is None else lambda: _clipped_step(model, optimizer, grad_clip)
     # where a minibatch comes from
     if native_batches:
-        batches, transitions = _native_batches(buf, minibatch, seed, gae, seats, kl is not None)
+        if native_update:
+            return _native_update(model, buf, optimizer, epochs, minibatch, seed, gae, seats, kl, coeff if kl is not None else None, grad_clip,
+                                  dict(clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, vf_clip=vf_clip))
+        batches, transitions = _native_batches(buf, minibatch, seed, gae, seats, kl is not None, shuffle)
     else:
         batches, transitions = _torch_batches(buf, minibatch, seed, gae)
     # which loss is evaluated: the torch expressions, whose gradients reach the parameters through their own graph ...

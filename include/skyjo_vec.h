@@ -654,6 +654,103 @@ int skyjo_vec_mlp_train_backward(int32_t obs_dim, int32_t out_dim, const float *
                                  const float *grad_out /* [m][out_dim] */, int64_t m, float *const grads[6] /* overwritten */,
                                  void *workspace, int64_t workspace_bytes, void *stream);
 
+/* An epoch's shuffled order of a selection, on device, without a sort: order_out[j] = index[perm(j)], 0 <= j < count, perm a keyed
+ * bijection of [0, count) that is a pure function of (count, seed, epoch, j) - one lane per j, no atomics, no cross-lane traffic.  Needs
+ * no handle: it runs on the current device, on `stream`.  1 <= count <= 2^30; count == 0 is no work (fault_out is still written);
+ * order_out must not alias index.  index holds row ids, which are not negative.  All arithmetic is uint32 with wrap-around:
+ *   fmix32(v):  v ^= v >> 16;  v *= 0x85EBCA6B;  v ^= v >> 13;  v *= 0xC2B2AE35;  v ^= v >> 16
+ *   key[r] = fmix32(seed_lo ^ fmix32(seed_hi ^ fmix32(epoch * 0x9E3779B9 + r))), r = 0 .. 5 (the halves of seed; computed on the host
+ *            and passed to the kernel by value)
+ *   b = the smallest even number >= 2 with 2^b >= count;  h = b / 2;  mask = 2^h - 1
+ *   E(x):  L = x >> h, R = x & mask;  six times, r = 0 .. 5:  (L, R) = (R, L ^ (fmix32(R + key[r]) & mask));  the result is (L << h) | R
+ *   perm(j) = the first of E(j), E(E(j)), ... that is below count (cycle walking; the domain 2^b is smaller than 4 count)
+ * The walk is capped at 1 024 applications of E.  A lane that hits the cap writes -1 to its order_out[j] - skyjo_vec_rollout_gather gives
+ * such a row zeros - and fault_out (device, one int64, written by EVERY call) receives the number of such lanes from a single-workgroup
+ * pass over order_out: 0 on success.  The longest walk tests/epoch_order_ref.py meets is 48: a non-zero count is a bug, not bad luck.
+ * SKYJO_E_INVALID (nothing is launched): a null pointer, count < 0 or > 2^30, a pointer that is not 8-byte aligned, order_out
+ * overlapping index. */
+int skyjo_vec_rollout_shuffle(const int64_t *index, int64_t count, uint64_t seed, uint32_t epoch, int64_t *order_out /* [count] */,
+                              int64_t *fault_out /* device, 1 */, void *stream);
+
+/* A whole PPO update behind one call: `epochs` passes over the selected rows of a rollout buffer in shuffled slices of `minibatch` rows
+ * (the last slice of an epoch may be short), every slice one learner step - exactly the launches the calls above make when a host loop
+ * issues them one by one, in the same order, with the same arguments, on the one stream:
+ *   1. skyjo_vec_rollout_gather of the slice (and skyjo_vec_rollout_gather_logits of `behaviour` with the KL term)
+ *   2. skyjo_vec_mlp_train_forward of the policy branch, then of the value branch
+ *   3. skyjo_vec_ppo_loss (skyjo_vec_ppo_loss_kl with the KL term)
+ *   4. skyjo_vec_mlp_train_backward of the policy branch, then of the value branch
+ *   5. skyjo_vec_grad_norm over the twelve gradients - the policy branch's six, then the value branch's - if clipping
+ *   6. skyjo_vec_mlp_adam_step (_clipped if clipping) of the policy net, then of the value net, with step first_step + k, k counting
+ *      the call's steps from 0 across the epochs
+ *   7. one wavefront that adds the step to the epoch's statistics
+ * so the parameters, the Adam states and both packed nets end with the bits of that host loop.  Epoch e takes orders[e] where orders is
+ * given, and otherwise shuffles index with skyjo_vec_rollout_shuffle(seed, e) into the workspace.  The call allocates nothing, copies
+ * nothing to the host, does not synchronise and has no host control flow that depends on device data; EVERY check of every stage runs
+ * before the first launch - an update runs whole or not at all.  count == 0 launches the zeroing of epoch_stats_out and fault_out alone.
+ *
+ * skyjo_vec_ppo_update_args (the caller fills every field; pointers are device memory unless noted):
+ *   records, layout, T, actions, logp, values, value_stride, advantages, value_targets   the buffer, as for skyjo_vec_rollout_gather
+ *   behaviour      float32 [T * num_envs][26] or NULL: NULL - no KL term; otherwise skyjo_vec_ppo_loss_kl with kl_coeff
+ *   index, count   the selection (skyjo_vec_rollout_select): count <= T * num_envs, count <= 2^30; index may be NULL with orders
+ *   adv_mean, adv_std   host scalars, as skyjo_vec_rollout_gather takes them: finite, adv_std > 0
+ *   epochs >= 1, minibatch >= 1, seed;  orders: NULL or int64 [epochs][count], used instead of the shuffle
+ *   clip, vf_coef, ent_coef, vf_clip, kl_coeff   the head's, with the ranges of skyjo_vec_ppo_loss / _kl
+ *   policy_net, value_net   the packed nets (26 outputs and 1, the engine's observation, the engine's device);  policy_params /
+ *                  value_params: their six float32 master tensors, host arrays of device pointers as for skyjo_vec_mlp_adam_step;
+ *                  policy_state / value_state with their byte counts: the Adam states
+ *   lr, beta1, beta2, eps   as for skyjo_vec_mlp_adam_step;  first_step >= 1: the step number of the call's first step
+ *   max_grad_norm  <= 0 or NaN: no clipping (stage 5 is not launched);  +inf: measure only;  otherwise as for skyjo_vec_grad_norm
+ * workspace: caller-owned, 16-byte aligned, at least skyjo_vec_ppo_update_workspace_bytes(h, count, minibatch, with_kl) bytes (a size that
+ * grows with count: one allocation for the largest count serves every smaller one).  It holds the minibatch columns, both branches'
+ * training workspaces and outputs, the head's gradients, statistics and scratch, the twelve gradients (each 16-byte aligned), the
+ * (norm, coefficient) pair, the order, the accumulators and the shuffle's fault word; nothing in it is an input.
+ * epoch_stats_out: double [epochs][SKYJO_UPDATE_STATS], one row per epoch, written after the epoch's last step:
+ *   [0 .. 5]  loss, policy_loss, vf_loss, entropy, kl, clip_fraction: sum over the steps of (the head's statistic * m) / max(seen, 1),
+ *             m the step's rows and seen their sum - a double product and a double add per step
+ *   [6]       action_kl, likewise; 0.0 without the KL term
+ *   [7]       the mean over the epoch's steps of the norm before clipping, (double)norm added per step; 0.0 without clipping
+ *   [8]       the share of steps whose coefficient was below 1, (double)(coef < 1.0f) added per step; 0.0 without clipping
+ *   [9]       seen
+ * Both quotients are formed as x * (1.0 / n), the reciprocal a host double - as torch divides a device tensor by a host scalar.
+ * fault_out (device, one int64): the sum of the epochs' skyjo_vec_rollout_shuffle fault counts; 0 with orders.
+ * SKYJO_E_INVALID (nothing is launched): what any stage refuses for these arguments - null pointers, alignments, state and workspace
+ * sizes, the hyper-parameter ranges - and epochs, minibatch or first_step < 1, count outside 0 .. min(2^30, T * num_envs), a net on
+ * another device, with another observation size or the wrong number of outputs. */
+#define SKYJO_UPDATE_STATS 10
+typedef struct skyjo_vec_ppo_update_args {
+  const void *records;
+  const int32_t *actions;
+  const float *logp;
+  const float *values;
+  const float *advantages;
+  const float *value_targets;
+  const float *behaviour; /* may be NULL */
+  const int64_t *index;
+  const int64_t *orders; /* may be NULL */
+  skyjo_vec_mlp *policy_net;
+  skyjo_vec_mlp *value_net;
+  float *policy_params[6];
+  float *value_params[6];
+  void *policy_state;
+  void *value_state;
+  int64_t policy_state_bytes;
+  int64_t value_state_bytes;
+  int64_t count;
+  int64_t minibatch;
+  int64_t first_step;
+  uint64_t seed;
+  int32_t layout;
+  int32_t T;
+  int32_t value_stride;
+  int32_t epochs;
+  float adv_mean, adv_std;
+  float clip, vf_coef, ent_coef, vf_clip, kl_coeff;
+  float lr, beta1, beta2, eps, max_grad_norm;
+} skyjo_vec_ppo_update_args;
+int64_t skyjo_vec_ppo_update_workspace_bytes(const skyjo_vec *h, int64_t count, int64_t minibatch, int32_t with_kl); /* 0 for invalid arguments */
+int skyjo_vec_ppo_update(skyjo_vec *h, const skyjo_vec_ppo_update_args *a, void *workspace, int64_t workspace_bytes,
+                         double *epoch_stats_out /* device, [epochs][SKYJO_UPDATE_STATS] */, int64_t *fault_out /* device, 1 */, void *stream);
+
 /* Arena rollouts: the evaluation path beside skyjo_vec_model_rollout.  Every SEAT has a policy of its own - what the reference's script
  * does when it trains one policy per seat (rlskyjo/models/train_model_simple_rllib.py:43-49) and afterwards plays them with
  * logits.argmax() (:123-130) - and a seat may play policy_ra instead (rlskyjo/models/random_admissible_policy.py:26-28).  In self-play

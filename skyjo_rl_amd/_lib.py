@@ -78,6 +78,20 @@ class SeatPolicy(C.Structure):  # skyjo_vec_seat_policy
 
 SEAT_SAMPLE, SEAT_GREEDY, SEAT_RANDOM = 0, 1, 2  # SKYJO_SEAT_*
 
+
+class PPOUpdateArgs(C.Structure):  # skyjo_vec_ppo_update_args, field for field (tests/test_epoch_order_ref.py compares the sizes)
+    _fields_ = ([(n, C.c_void_p) for n in ("records", "actions", "logp", "values", "advantages", "value_targets", "behaviour", "index",
+                                           "orders", "policy_net", "value_net")]
+                + [("policy_params", C.c_void_p * 6), ("value_params", C.c_void_p * 6), ("policy_state", C.c_void_p), ("value_state", C.c_void_p)]
+                + [(n, C.c_int64) for n in ("policy_state_bytes", "value_state_bytes", "count", "minibatch", "first_step")]
+                + [("seed", C.c_uint64)] + [(n, C.c_int32) for n in ("layout", "T", "value_stride", "epochs")]
+                + [(n, C.c_float) for n in ("adv_mean", "adv_std", "clip", "vf_coef", "ent_coef", "vf_clip", "kl_coeff", "lr", "beta1", "beta2",
+                                            "eps", "max_grad_norm")])
+
+
+UPDATE_STATS = 10  # SKYJO_UPDATE_STATS: the doubles of one epoch's row of skyjo_vec_ppo_update's statistics
+E_INVALID = -1  # SKYJO_E_INVALID
+
 # option ids / record layouts of include/skyjo_vec.h
 OPT_RECORD_LAYOUT, REC_ROW_MAJOR, REC_TILE_PLANAR, REC_TILE_PLANAR_ALL = 6, 0, 1, 2
 TGT_HAS_TARGET, TGT_EPISODE_KNOWN = 1, 2  # SKYJO_TGT_*: bits of skyjo_vec_rollout_targets' flags column
@@ -133,6 +147,9 @@ SIGNATURES = {
     "skyjo_vec_mlp_train_workspace_bytes": (I64, [I32, I32, I64]),
     "skyjo_vec_mlp_train_forward": (C.c_int, [I32, I32, VP, VP, I64, VP, VP, I64, VP]),
     "skyjo_vec_mlp_train_backward": (C.c_int, [I32, I32, VP, VP, VP, I64, VP, VP, I64, VP]),
+    "skyjo_vec_rollout_shuffle": (C.c_int, [VP, I64, U64, U32, VP, VP, VP]),
+    "skyjo_vec_ppo_update_workspace_bytes": (I64, [VP, I64, I64, I32]),
+    "skyjo_vec_ppo_update": (C.c_int, [VP, C.POINTER(PPOUpdateArgs), VP, I64, VP, VP, VP]),
     "skyjo_vec_arena_workspace_bytes": (I64, [VP, I32]),
     "skyjo_vec_arena_select": (C.c_int, [VP, C.POINTER(SeatPolicy), VP, I32, U64, U64, VP, VP, I64, VP]),
     "skyjo_vec_arena_rollout": (C.c_int, [VP, C.POINTER(SeatPolicy), I32, U64, U64, C.POINTER(RolloutBuffers), VP, I64, VP]),

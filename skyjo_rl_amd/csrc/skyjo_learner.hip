@@ -1,10 +1,12 @@
 // skyjo_learner.hip - the packed nets' handles and the learner behind the extern "C" boundary of include/skyjo_vec.h: skyjo_vec_mlp_*,
-// skyjo_vec_rollout_targets / _select / _gather / _gather_logits, skyjo_vec_ppo_loss / _kl, skyjo_vec_mlp_train_*, skyjo_vec_grad_norm, skyjo_vec_arena_* and skyjo_vec_episode_stats,
-// with their kernels (skyjo_update.h, skyjo_clip.h, skyjo_targets.h, skyjo_batches.h, skyjo_loss.h, skyjo_train.h, skyjo_arena.h; what they share: skyjo_learner_util.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
+// skyjo_vec_rollout_targets / _select / _gather / _gather_logits / _shuffle, skyjo_vec_ppo_loss / _kl, skyjo_vec_mlp_train_*, skyjo_vec_grad_norm, skyjo_vec_ppo_update,
+// skyjo_vec_arena_* and skyjo_vec_episode_stats,
+// with their kernels (skyjo_update.h, skyjo_clip.h, skyjo_targets.h, skyjo_batches.h, skyjo_loss.h, skyjo_train.h, skyjo_epoch.h, skyjo_arena.h; what they share: skyjo_learner_util.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
 // (skyjo_capi.hip, skyjo_device.h and its parts), and of an engine it sees what skyjo_host.h shows - the record layout, B, G, game_id0,
 // the device and the select scratch.  gfx950 only, no CPU path.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <new>
 #include <string>
@@ -17,6 +19,7 @@
 #include "skyjo_batches.h"
 #include "skyjo_loss.h"
 #include "skyjo_train.h"
+#include "skyjo_epoch.h"
 #include "skyjo_arena.h"
 
 extern "C" {
@@ -107,11 +110,20 @@ int64_t skyjo_vec_mlp_adam_state_bytes(const skyjo_vec_mlp *m) {
   return m ? (int64_t)(2 * sku_state_half(m->obs_dim, m->out_dim) * sizeof(float)) : 0;
 }
 
-// both Adam entries: the checks, the scalars and the launch.  coef: the clipped entry's coefficient on the device, or null
-static int adam_step(const char *who, skyjo_vec_mlp *m, float *const params[6], const float *const grads[6], void *state, int64_t state_bytes,
-                     float lr, float beta1, float beta2, float eps, int64_t step, const float *coef, void *stream) {
+// torch.optim.Adam's scalars of a step, in double from the float32 hyper-parameters and the step, rounded to float32 once
+static void adam_scalars(SkUpdArgs &a, float lr, float beta1, float beta2, float eps, int64_t step) {
+  const double b1 = (double)beta1, b2 = (double)beta2, t = (double)step;
+  a.w1 = (float)(1.0 - b1), a.beta2 = beta2, a.w2 = (float)(1.0 - b2);
+  a.step_size = (float)((double)lr / (1.0 - std::pow(b1, t)));
+  a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, t));
+  a.eps = eps;
+}
+
+// both Adam entries and skyjo_vec_ppo_update: the checks and the kernel's arguments, nothing launched.  coef: the clipped entry's
+// coefficient on the device, or null
+static int adam_check(const char *who, skyjo_vec_mlp *m, float *const params[6], const float *const grads[6], void *state, int64_t state_bytes,
+                      float lr, float beta1, float beta2, float eps, int64_t step, const float *coef, SkUpdArgs &a) {
   const std::string name(who);
-  SkUpdArgs a{};
   if (!m || !params || !grads || !state || !mlp_update_args(m, params, a)) return fail(SKYJO_E_INVALID, name + ": null argument");
   for (int i = 0; i < SKU_TENSORS; i++) {
     if (!grads[i]) return fail(SKYJO_E_INVALID, name + ": null gradient");
@@ -128,16 +140,20 @@ static int adam_step(const char *who, skyjo_vec_mlp *m, float *const params[6], 
     return fail(SKYJO_E_INVALID, name + ": state, w2, w3 and their gradients must be 16-byte aligned");
   a.coef = coef;
   a.m = (float *)state, a.v = a.m + sku_state_half(m->obs_dim, m->out_dim);
-  // torch.optim.Adam's scalars, in double from the float32 hyper-parameters and the step, rounded to float32 once
-  const double b1 = (double)beta1, b2 = (double)beta2, t = (double)step;
-  a.w1 = (float)(1.0 - b1), a.beta2 = beta2, a.w2 = (float)(1.0 - b2);
-  a.step_size = (float)((double)lr / (1.0 - std::pow(b1, t)));
-  a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, t));
-  a.eps = eps;
+  adam_scalars(a, lr, beta1, beta2, eps, step);
+  return SKYJO_OK;
+}
+static int adam_launch(const skyjo_vec_mlp *m, const SkUpdArgs &a, hipStream_t s) {
   DevGuard guard_(m->device_id);
-  hipLaunchKernelGGL(k_mlp_update<true>, dim3(SKU_BLOCKS), dim3(SKU_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_mlp_update<true>, dim3(SKU_BLOCKS), dim3(SKU_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
   return SKYJO_OK;
+}
+static int adam_step(const char *who, skyjo_vec_mlp *m, float *const params[6], const float *const grads[6], void *state, int64_t state_bytes,
+                     float lr, float beta1, float beta2, float eps, int64_t step, const float *coef, void *stream) {
+  SkUpdArgs a{};
+  if (int rc = adam_check(who, m, params, grads, state, state_bytes, lr, beta1, beta2, eps, step, coef, a)) return rc;
+  return adam_launch(m, a, (hipStream_t)stream);
 }
 
 int skyjo_vec_mlp_adam_step(skyjo_vec_mlp *m, float *const params[6], const float *const grads[6], void *state, int64_t state_bytes,
@@ -154,13 +170,12 @@ int skyjo_vec_mlp_adam_step_clipped(skyjo_vec_mlp *m, float *const params[6], co
 }
 
 // ---- the global L2 norm of a list of tensors and torch's clipping coefficient (include/skyjo_vec.h: skyjo_vec_grad_norm; skyjo_clip.h) ----
-int skyjo_vec_grad_norm(const float *const tensors[], const int64_t counts[], int32_t n, float max_norm, float *out2, void *stream) {
-  static const char *who = "skyjo_vec_grad_norm";
+// the checks and the kernel's arguments, nothing launched
+static int grad_norm_check(const char *who, const float *const tensors[], const int64_t counts[], int32_t n, float max_norm, float *out2, SkNormArgs &a) {
   if (!tensors || !counts || !out2) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
   if (n < 1 || n > SKC_MAX_SEGMENTS) return fail(SKYJO_E_INVALID, std::string(who) + ": n must lie in 1 .. 32");
   if (!(max_norm > 0.f)) return fail(SKYJO_E_INVALID, std::string(who) + ": max_norm must be greater than 0 (+inf: measure only)");
   if ((uintptr_t)out2 & 3) return fail(SKYJO_E_INVALID, std::string(who) + ": out2 is not aligned to its element size");
-  SkNormArgs a{};
   for (int i = 0; i < n; i++) {
     if (counts[i] < 0) return fail(SKYJO_E_INVALID, std::string(who) + ": a count is negative");
     if (!tensors[i] && counts[i] > 0) return fail(SKYJO_E_INVALID, std::string(who) + ": a null tensor with a count greater than 0");
@@ -168,9 +183,17 @@ int skyjo_vec_grad_norm(const float *const tensors[], const int64_t counts[], in
     a.ptr[i] = tensors[i], a.count[i] = (long long)counts[i];
   }
   a.n = n, a.max_norm = max_norm, a.out = out2;
-  hipLaunchKernelGGL(k_grad_norm, dim3(1), dim3(SKC_THREADS), 0, (hipStream_t)stream, a);
+  return SKYJO_OK;
+}
+static int grad_norm_launch(const SkNormArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_grad_norm, dim3(1), dim3(SKC_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
   return SKYJO_OK;
+}
+int skyjo_vec_grad_norm(const float *const tensors[], const int64_t counts[], int32_t n, float max_norm, float *out2, void *stream) {
+  SkNormArgs a{};
+  if (int rc = grad_norm_check("skyjo_vec_grad_norm", tensors, counts, n, max_norm, out2, a)) return rc;
+  return grad_norm_launch(a, (hipStream_t)stream);
 }
 
 int64_t skyjo_vec_mlp_packed_bytes(const skyjo_vec_mlp *m) {
@@ -328,48 +351,74 @@ int skyjo_vec_rollout_select_seats(skyjo_vec *h, const void *records, int32_t la
   return select_rows(h, &st, flags, n_rows, require_bits, advantages, index_out, count_out, moments_out, (hipStream_t)stream);
 }
 
-int skyjo_vec_rollout_gather(skyjo_vec *h, const void *records, int32_t layout, int32_t T, const int64_t *index, int64_t m,
-                             const int32_t *actions, const float *logp, const float *values, int32_t value_stride, const float *advantages,
-                             const float *value_targets, float adv_mean, float adv_std, float *obs_out, float *logmask_out,
-                             int64_t *actions_out, float *logp_out, float *advantages_out, float *value_targets_out, float *values_out,
-                             uint8_t *seats_out, void *stream) {
+// skyjo_vec_rollout_gather and skyjo_vec_ppo_update: the checks and the kernel's arguments, nothing launched
+static int gather_check(const char *who, skyjo_vec *h, const void *records, int32_t layout, int32_t T, const int64_t *index, int64_t m,
+                        const int32_t *actions, const float *logp, const float *values, int32_t value_stride, const float *advantages,
+                        const float *value_targets, float adv_mean, float adv_std, float *obs_out, float *logmask_out, int64_t *actions_out,
+                        float *logp_out, float *advantages_out, float *value_targets_out, float *values_out, uint8_t *seats_out, SkGatherArgs &a) {
+  const std::string name(who);
   if (!h || !records || !index || !actions || !logp || !values || !advantages || !value_targets || !obs_out || !logmask_out ||
       !actions_out || !logp_out || !advantages_out || !value_targets_out || !values_out || !seats_out)
-    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather: null argument");
-  if (m < 0 || T < 1 || value_stride < 1) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather: m must not be negative, T and value_stride at least 1");
+    return fail(SKYJO_E_INVALID, name + ": null argument");
+  if (m < 0 || T < 1 || value_stride < 1) return fail(SKYJO_E_INVALID, name + ": m must not be negative, T and value_stride at least 1");
   if (int rc = check_layout(layout)) return rc;
   if (!std::isfinite(adv_mean) || !std::isfinite(adv_std) || !(adv_std > 0.f))
-    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather: adv_mean must be finite, adv_std finite and greater than 0");
+    return fail(SKYJO_E_INVALID, name + ": adv_mean must be finite, adv_std finite and greater than 0");
   if ((((uintptr_t)records | (uintptr_t)obs_out | (uintptr_t)logmask_out) & 15) != 0)
-    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather: records, obs_out and logmask_out must be 16-byte aligned");
-  if (m == 0) return SKYJO_OK;
+    return fail(SKYJO_E_INVALID, name + ": records, obs_out and logmask_out must be 16-byte aligned");
   const SkEngineView e = sk_engine_view(h);
-  DevGuard guard_(e.device_id);
   const SkLayout &L = *e.L;
   static_assert(SK_GATHER_MAX_PIECES * 16 >= ((19 + 12 * SKYJO_MAX_PLAYERS + 3) & ~3) + 32, "the largest record fits k_gather_rows' LDS image");
-  SkGatherArgs a{};
   a.rec = sk_records(e, records, layout), a.index = (const long long *)index, a.actions = actions, a.logp = logp, a.values = values;
   a.adv = advantages, a.vt = value_targets;
   a.obs_out = obs_out, a.lm_out = logmask_out, a.act_out = (long long *)actions_out, a.logp_out = logp_out, a.adv_out = advantages_out;
   a.vt_out = value_targets_out, a.val_out = values_out, a.seat_out = seats_out;
   a.m = m, a.n_rows = (long long)T * e.B, a.vstride = value_stride, a.D = L.D, a.Dp = L.Dp;
   a.mean = adv_mean, a.std = adv_std;
-  hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((m + SK_GATHER_ROWS - 1) / SK_GATHER_ROWS)), dim3(SK_GATHER_THREADS), 0, (hipStream_t)stream, a);
+  return SKYJO_OK;
+}
+// a.m >= 1 rows from a.index, on the current device
+static int gather_launch(const SkGatherArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((a.m + SK_GATHER_ROWS - 1) / SK_GATHER_ROWS)), dim3(SK_GATHER_THREADS), 0, s, a);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+int skyjo_vec_rollout_gather(skyjo_vec *h, const void *records, int32_t layout, int32_t T, const int64_t *index, int64_t m,
+                             const int32_t *actions, const float *logp, const float *values, int32_t value_stride, const float *advantages,
+                             const float *value_targets, float adv_mean, float adv_std, float *obs_out, float *logmask_out,
+                             int64_t *actions_out, float *logp_out, float *advantages_out, float *value_targets_out, float *values_out,
+                             uint8_t *seats_out, void *stream) {
+  SkGatherArgs a{};
+  if (int rc = gather_check("skyjo_vec_rollout_gather", h, records, layout, T, index, m, actions, logp, values, value_stride, advantages, value_targets,
+                            adv_mean, adv_std, obs_out, logmask_out, actions_out, logp_out, advantages_out, value_targets_out, values_out, seats_out, a))
+    return rc;
+  if (m == 0) return SKYJO_OK;
+  DevGuard guard_(sk_engine_view(h).device_id);
+  return gather_launch(a, (hipStream_t)stream);
+}
+
+// skyjo_vec_rollout_gather_logits and skyjo_vec_ppo_update: the checks, nothing launched
+static int gather_logits_check(const char *who, const float *column, int64_t n_rows, const int64_t *index, int64_t m, float *out) {
+  const std::string name(who);
+  if (!column || !index || !out) return fail(SKYJO_E_INVALID, name + ": null argument");
+  if (m < 0 || n_rows < 0) return fail(SKYJO_E_INVALID, name + ": m and n_rows must not be negative");
+  if (!aligned16(out) || ((uintptr_t)column & 3) != 0 || ((uintptr_t)index & 7) != 0)
+    return fail(SKYJO_E_INVALID, name + ": out must be 16-byte aligned, column and index aligned to their element size");
+  if (m > (int64_t)SK_GATHER_ROWS * 0x7fffffff) return fail(SKYJO_E_INVALID, name + ": m is out of range");
+  return SKYJO_OK;
+}
+static int gather_logits_launch(const float *column, int64_t n_rows, const int64_t *index, int64_t m, float *out, hipStream_t s) {
+  hipLaunchKernelGGL(k_gather_logits, dim3((unsigned)((m + SK_GATHER_ROWS - 1) / SK_GATHER_ROWS)), dim3(SK_GATHER_THREADS), 0, s, column,
+                     (long long)n_rows, (const long long *)index, (long long)m, out);
   HIPCHK(hipGetLastError());
   return SKYJO_OK;
 }
 
 int skyjo_vec_rollout_gather_logits(const float *column, int64_t n_rows, const int64_t *index, int64_t m, float *out, void *stream) {
-  if (!column || !index || !out) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather_logits: null argument");
-  if (m < 0 || n_rows < 0) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather_logits: m and n_rows must not be negative");
-  if (!aligned16(out) || ((uintptr_t)column & 3) != 0 || ((uintptr_t)index & 7) != 0)
-    return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather_logits: out must be 16-byte aligned, column and index aligned to their element size");
+  if (int rc = gather_logits_check("skyjo_vec_rollout_gather_logits", column, n_rows, index, m, out)) return rc;
   if (m == 0) return SKYJO_OK;
-  if (m > (int64_t)SK_GATHER_ROWS * 0x7fffffff) return fail(SKYJO_E_INVALID, "skyjo_vec_rollout_gather_logits: m is out of range");
-  hipLaunchKernelGGL(k_gather_logits, dim3((unsigned)((m + SK_GATHER_ROWS - 1) / SK_GATHER_ROWS)), dim3(SK_GATHER_THREADS), 0, (hipStream_t)stream,
-                     column, (long long)n_rows, (const long long *)index, (long long)m, out);
-  HIPCHK(hipGetLastError());
-  return SKYJO_OK;
+  return gather_logits_launch(column, n_rows, index, m, out, (hipStream_t)stream);
 }
 
 // ---- the PPO loss head of a learner minibatch (include/skyjo_vec.h: skyjo_vec_ppo_loss, skyjo_vec_ppo_loss_kl; the kernels: skyjo_loss.h) ----
@@ -381,11 +430,12 @@ static int64_t loss_scratch_bytes(int64_t m, int stats) {
 int64_t skyjo_vec_ppo_loss_scratch_bytes(int64_t m) { return loss_scratch_bytes(m, SK_LOSS_STATS); }
 int64_t skyjo_vec_ppo_loss_kl_scratch_bytes(int64_t m) { return loss_scratch_bytes(m, SK_LOSS_KL_STATS); }
 
-// both entries: the checks, then the main launch and the finish.  KL: old_logits and kl_coeff take part, seven statistics
-static int ppo_loss(const char *who, const bool KL, const float *logits, const float *log_mask, const float *old_logits, const float *value,
-                    const int64_t *actions, const float *logp_old, const float *advantages, const float *value_targets,
-                    const float *values_old, int64_t m, float clip, float vf_coef, float ent_coef, float vf_clip, float kl_coeff,
-                    float *grad_logits_out, float *grad_value_out, double *stats_out, void *scratch, int64_t scratch_bytes, void *stream) {
+// both entries and skyjo_vec_ppo_update: the checks and the kernel's arguments, nothing launched.  KL: old_logits and kl_coeff take
+// part, seven statistics
+static int ppo_loss_check(const char *who, const bool KL, const float *logits, const float *log_mask, const float *old_logits, const float *value,
+                          const int64_t *actions, const float *logp_old, const float *advantages, const float *value_targets,
+                          const float *values_old, int64_t m, float clip, float vf_coef, float ent_coef, float vf_clip, float kl_coeff,
+                          float *grad_logits_out, float *grad_value_out, double *stats_out, void *scratch, int64_t scratch_bytes, SkLossArgs &a) {
   const std::string name(who);
   if (!logits || !log_mask || (KL && !old_logits) || !value || !actions || !logp_old || !advantages || !value_targets || !values_old ||
       !grad_logits_out || !grad_value_out || !stats_out || !scratch)
@@ -403,7 +453,6 @@ static int ppo_loss(const char *who, const bool KL, const float *logits, const f
   const int NS = KL ? SK_LOSS_KL_STATS : SK_LOSS_STATS;
   if (scratch_bytes < loss_scratch_bytes(m, NS)) return fail(SKYJO_E_INVALID, name + ": scratch is smaller than " + name + "_scratch_bytes(m)");
   static_assert(SK_LOSS_ROWS % 2 == 0 && SK_LOSS_ROWS <= SK_LOSS_THREADS, "a run is whole 16-byte pieces and every row has its lane");
-  SkLossArgs a{};
   a.logits = logits, a.log_mask = log_mask, a.old_logits = old_logits, a.value = value, a.actions = (const long long *)actions;
   a.logp_old = logp_old, a.adv = advantages, a.vt = value_targets, a.v_old = values_old, a.g_logits = grad_logits_out, a.g_value = grad_value_out;
   a.partial = (double *)scratch, a.m = m;
@@ -411,16 +460,29 @@ static int ppo_loss(const char *who, const bool KL, const float *logits, const f
   a.vf_coef = vf_coef, a.ent_coef = ent_coef;
   a.vf_clip = (std::isfinite(vf_clip) && vf_clip > 0.f) ? vf_clip : 0.f;
   a.kl_coeff = kl_coeff;
-  const int64_t nb = (m + SK_LOSS_ROWS - 1) / SK_LOSS_ROWS;
-  hipStream_t s = (hipStream_t)stream;
+  return SKYJO_OK;
+}
+// the main launch and the finish
+static int ppo_loss_launch(const bool KL, const SkLossArgs &a, double *stats_out, hipStream_t s) {
+  const int64_t m = a.m, nb = (m + SK_LOSS_ROWS - 1) / SK_LOSS_ROWS;
   const dim3 grid((unsigned)nb), one(1), threads(SK_LOSS_THREADS), fin(SK_LOSS_FIN_THREADS);
   if (KL) hipLaunchKernelGGL(k_ppo_loss<true>, grid, threads, 0, s, a);
   else hipLaunchKernelGGL(k_ppo_loss<false>, grid, threads, 0, s, a);
   HIPCHK(hipGetLastError());
-  if (KL) hipLaunchKernelGGL(k_ppo_loss_finish<SK_LOSS_KL_STATS>, one, fin, 0, s, (const double *)scratch, (int)nb, (double)m, stats_out);
-  else hipLaunchKernelGGL(k_ppo_loss_finish<SK_LOSS_STATS>, one, fin, 0, s, (const double *)scratch, (int)nb, (double)m, stats_out);
+  if (KL) hipLaunchKernelGGL(k_ppo_loss_finish<SK_LOSS_KL_STATS>, one, fin, 0, s, (const double *)a.partial, (int)nb, (double)m, stats_out);
+  else hipLaunchKernelGGL(k_ppo_loss_finish<SK_LOSS_STATS>, one, fin, 0, s, (const double *)a.partial, (int)nb, (double)m, stats_out);
   HIPCHK(hipGetLastError());
   return SKYJO_OK;
+}
+static int ppo_loss(const char *who, const bool KL, const float *logits, const float *log_mask, const float *old_logits, const float *value,
+                    const int64_t *actions, const float *logp_old, const float *advantages, const float *value_targets,
+                    const float *values_old, int64_t m, float clip, float vf_coef, float ent_coef, float vf_clip, float kl_coeff,
+                    float *grad_logits_out, float *grad_value_out, double *stats_out, void *scratch, int64_t scratch_bytes, void *stream) {
+  SkLossArgs a{};
+  if (int rc = ppo_loss_check(who, KL, logits, log_mask, old_logits, value, actions, logp_old, advantages, value_targets, values_old, m, clip, vf_coef,
+                              ent_coef, vf_clip, kl_coeff, grad_logits_out, grad_value_out, stats_out, scratch, scratch_bytes, a))
+    return rc;
+  return ppo_loss_launch(KL, a, stats_out, (hipStream_t)stream);
 }
 
 int skyjo_vec_ppo_loss(const float *logits, const float *log_mask, const float *value, const int64_t *actions, const float *logp_old,
@@ -477,24 +539,31 @@ int64_t skyjo_vec_mlp_train_workspace_bytes(int32_t obs_dim, int32_t out_dim, in
   return (int64_t)sizeof(float) * (4 * m * SKT_H + train_chunks(m) * SKT_PART);
 }
 
-int skyjo_vec_mlp_train_forward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, int64_t m, float *out,
-                                void *workspace, int64_t workspace_bytes, void *stream) {
-  static const char *who = "skyjo_vec_mlp_train_forward";
-  SkTrainArgs a{};
+// the two calls and skyjo_vec_ppo_update: the checks and the kernels' arguments, nothing launched - and the launches
+static int train_forward_check(const char *who, int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, int64_t m, float *out,
+                               void *workspace, int64_t workspace_bytes, SkTrainArgs &a) {
   if (!out) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
   if (int rc = train_args(who, obs_dim, out_dim, params, x, m, workspace, workspace_bytes, a)) return rc;
   if ((uintptr_t)out & 3) return fail(SKYJO_E_INVALID, std::string(who) + ": out is not aligned to its element size");
   a.out = out;
-  const unsigned tiles = (unsigned)((m + SKT_TILE_ROWS - 1) / SKT_TILE_ROWS);
-  hipLaunchKernelGGL(k_mlp_train_fwd, dim3(tiles), dim3(SKT_THREADS), 0, (hipStream_t)stream, a);
+  return SKYJO_OK;
+}
+static int train_forward_launch(const SkTrainArgs &a, hipStream_t s) {
+  const unsigned tiles = (unsigned)((a.m + SKT_TILE_ROWS - 1) / SKT_TILE_ROWS);
+  hipLaunchKernelGGL(k_mlp_train_fwd, dim3(tiles), dim3(SKT_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
   return SKYJO_OK;
 }
 
-int skyjo_vec_mlp_train_backward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, const float *grad_out,
-                                 int64_t m, float *const grads[6], void *workspace, int64_t workspace_bytes, void *stream) {
-  static const char *who = "skyjo_vec_mlp_train_backward";
+int skyjo_vec_mlp_train_forward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, int64_t m, float *out,
+                                void *workspace, int64_t workspace_bytes, void *stream) {
   SkTrainArgs a{};
+  if (int rc = train_forward_check("skyjo_vec_mlp_train_forward", obs_dim, out_dim, params, x, m, out, workspace, workspace_bytes, a)) return rc;
+  return train_forward_launch(a, (hipStream_t)stream);
+}
+
+static int train_backward_check(const char *who, int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, const float *grad_out,
+                                int64_t m, float *const grads[6], void *workspace, int64_t workspace_bytes, SkTrainArgs &a) {
   if (!grad_out || !grads) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
   for (int i = 0; i < 6; i++)
     if (!grads[i]) return fail(SKYJO_E_INVALID, std::string(who) + ": null gradient");
@@ -505,14 +574,234 @@ int skyjo_vec_mlp_train_backward(int32_t obs_dim, int32_t out_dim, const float *
     a.grads[i] = grads[i];
   }
   a.g = grad_out;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned tiles = (unsigned)((m + SKT_TILE_ROWS - 1) / SKT_TILE_ROWS);
+  return SKYJO_OK;
+}
+static int train_backward_launch(const SkTrainArgs &a, hipStream_t s) {
+  const unsigned tiles = (unsigned)((a.m + SKT_TILE_ROWS - 1) / SKT_TILE_ROWS);
   hipLaunchKernelGGL(k_mlp_train_bwd_rows, dim3(tiles), dim3(SKT_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_mlp_train_bwd_weights, dim3((unsigned)a.chunks, SKT_SLICES), dim3(SKT_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_mlp_train_bwd_finish, dim3((SKT_PART + SKT_THREADS - 1) / SKT_THREADS), dim3(SKT_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+int skyjo_vec_mlp_train_backward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, const float *grad_out,
+                                 int64_t m, float *const grads[6], void *workspace, int64_t workspace_bytes, void *stream) {
+  SkTrainArgs a{};
+  if (int rc = train_backward_check("skyjo_vec_mlp_train_backward", obs_dim, out_dim, params, x, grad_out, m, grads, workspace, workspace_bytes, a))
+    return rc;
+  return train_backward_launch(a, (hipStream_t)stream);
+}
+
+// ---- an epoch's order and a whole PPO update behind one call (include/skyjo_vec.h: skyjo_vec_rollout_shuffle, skyjo_vec_ppo_update;
+// the kernels of their own: skyjo_epoch.h; every stage through the launchers above) ----
+namespace {
+
+int shuffle_check(const char *who, const int64_t *index, int64_t count, const int64_t *order_out, const int64_t *fault_out) {
+  const std::string name(who);
+  if (!index || !order_out || !fault_out) return fail(SKYJO_E_INVALID, name + ": null argument");
+  if (count < 0 || count > SKE_MAX_COUNT) return fail(SKYJO_E_INVALID, name + ": count must lie in 0 .. 2^30");
+  if ((((uintptr_t)index | (uintptr_t)order_out | (uintptr_t)fault_out) & 7) != 0)
+    return fail(SKYJO_E_INVALID, name + ": index, order_out and fault_out must be 8-byte aligned");
+  if (index == order_out || (index < order_out ? index + count > order_out : order_out + count > index))
+    return fail(SKYJO_E_INVALID, name + ": order_out must not alias index");
+  return SKYJO_OK;
+}
+
+// the order of (seed, epoch) and the count of its capped walks, on the current device; count == 0 writes the zero count alone
+int shuffle_launch(const int64_t *index, int64_t count, uint64_t seed, uint32_t epoch, int64_t *order_out, int64_t *fault_out, hipStream_t s) {
+  if (count > 0) {
+    SkOrderArgs a{};
+    ske_plan(seed, epoch, count, a);
+    a.index = (const long long *)index, a.order = (long long *)order_out;
+    hipLaunchKernelGGL(k_epoch_order, dim3((unsigned)((count + SKE_ORDER_THREADS - 1) / SKE_ORDER_THREADS)), dim3(SKE_ORDER_THREADS), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_epoch_faults, dim3(1), dim3(SKE_FAULT_THREADS), 0, s, (const long long *)order_out, (long long)count, (long long *)fault_out);
+  HIPCHK(hipGetLastError());
+  return SKYJO_OK;
+}
+
+// skyjo_vec_ppo_update's workspace: every piece at a multiple of 256 bytes (the twelve gradients 16-byte aligned, as skyjo_vec_grad_norm's
+// order of additions has torch's allocations).  R = max(min(minibatch, count), 1) rows; every size grows with count
+struct UpdLayout {
+  size_t obs, logmask, actions, logp, adv, vt, val, seats, old_logits, ws[2], out[2], g_logits, g_value, loss_stats, loss_scratch, grads[2][SKU_TENSORS],
+      pair, order, acc, fault, total;
+  int64_t ws_bytes[2], loss_scratch_bytes, rows;
+};
+constexpr int kUpdOut[2] = {SKYJO_NUM_ACTIONS, 1};  // the policy branch's outputs and the value branch's
+
+UpdLayout upd_layout(int D, int64_t count, int64_t minibatch, bool kl) {
+  UpdLayout u{};
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    const size_t here = at;
+    at += (bytes + 255) & ~(size_t)255;
+    return here;
+  };
+  const int64_t R = u.rows = std::max<int64_t>(std::min(minibatch, count), 1);
+  const size_t f = sizeof(float);
+  u.obs = take(R * D * f), u.logmask = take(R * SKYJO_NUM_ACTIONS * f), u.actions = take(R * sizeof(int64_t));
+  u.logp = take(R * f), u.adv = take(R * f), u.vt = take(R * f), u.val = take(R * f), u.seats = take(R);
+  u.old_logits = take(kl ? R * SKYJO_NUM_ACTIONS * f : 0);
+  for (int b = 0; b < 2; b++) {
+    u.ws_bytes[b] = skyjo_vec_mlp_train_workspace_bytes(D, kUpdOut[b], R);
+    u.ws[b] = take((size_t)u.ws_bytes[b]), u.out[b] = take(R * kUpdOut[b] * f);
+  }
+  u.g_logits = take(R * SKYJO_NUM_ACTIONS * f), u.g_value = take(R * f), u.loss_stats = take(SK_LOSS_KL_STATS * sizeof(double));
+  u.loss_scratch_bytes = loss_scratch_bytes(R, kl ? SK_LOSS_KL_STATS : SK_LOSS_STATS);
+  u.loss_scratch = take((size_t)u.loss_scratch_bytes);
+  for (int b = 0; b < 2; b++)
+    for (int i = 0; i < SKU_TENSORS; i++) u.grads[b][i] = take(sku_tensor_elems(i, D, kUpdOut[b]) * f);
+  u.pair = take(2 * f), u.order = take((size_t)count * sizeof(int64_t)), u.acc = take(SKE_ACC * sizeof(double)), u.fault = take(sizeof(int64_t));
+  u.total = at;
+  return u;
+}
+
+bool upd_sizes_valid(int64_t count, int64_t minibatch) { return count >= 0 && count <= SKE_MAX_COUNT && minibatch >= 1; }
+
+// the arguments of the stages whose views depend on the slice's row count m: both branches' forward and backward, and the head
+struct UpdSlice {
+  SkTrainArgs fwd[2], bwd[2];
+  SkLossArgs loss;
+};
+
+}  // namespace
+
+int skyjo_vec_rollout_shuffle(const int64_t *index, int64_t count, uint64_t seed, uint32_t epoch, int64_t *order_out, int64_t *fault_out,
+                              void *stream) {
+  if (int rc = shuffle_check("skyjo_vec_rollout_shuffle", index, count, order_out, fault_out)) return rc;
+  return shuffle_launch(index, count, seed, epoch, order_out, fault_out, (hipStream_t)stream);
+}
+
+int64_t skyjo_vec_ppo_update_workspace_bytes(const skyjo_vec *h, int64_t count, int64_t minibatch, int32_t with_kl) {
+  if (!h || !upd_sizes_valid(count, minibatch)) return 0;
+  return (int64_t)upd_layout(sk_engine_view(h).L->D, count, minibatch, with_kl != 0).total;
+}
+
+int skyjo_vec_ppo_update(skyjo_vec *h, const skyjo_vec_ppo_update_args *a, void *workspace, int64_t workspace_bytes, double *epoch_stats_out,
+                         int64_t *fault_out, void *stream) {
+  static const char *who = "skyjo_vec_ppo_update";
+  const std::string name(who);
+  // ---- every check of every stage, before the first launch: an update runs whole or not at all ----
+  if (!h || !a || !workspace || !epoch_stats_out || !fault_out) return fail(SKYJO_E_INVALID, name + ": null argument");
+  if (!a->policy_net || !a->value_net || !a->policy_state || !a->value_state) return fail(SKYJO_E_INVALID, name + ": null net or Adam state");
+  if (a->epochs < 1 || a->minibatch < 1 || a->first_step < 1) return fail(SKYJO_E_INVALID, name + ": epochs, minibatch and first_step must be at least 1");
+  if (!upd_sizes_valid(a->count, a->minibatch)) return fail(SKYJO_E_INVALID, name + ": count must lie in 0 .. 2^30");
+  if (a->T < 1 || a->value_stride < 1) return fail(SKYJO_E_INVALID, name + ": T and value_stride must be at least 1");
+  if (int rc = check_layout(a->layout)) return rc;
+  const SkEngineView e = sk_engine_view(h);
+  const int D = e.L->D;
+  const int64_t n_rows = (int64_t)a->T * e.B, count = a->count, mb = a->minibatch;
+  if (count > n_rows) return fail(SKYJO_E_INVALID, name + ": count exceeds T * num_envs");
+  if ((((uintptr_t)epoch_stats_out | (uintptr_t)fault_out | (uintptr_t)a->index | (uintptr_t)a->orders) & 7) != 0)
+    return fail(SKYJO_E_INVALID, name + ": epoch_stats_out, fault_out, index and orders must be 8-byte aligned");
+  if (!aligned16(workspace)) return fail(SKYJO_E_INVALID, name + ": workspace must be 16-byte aligned");
+  skyjo_vec_mlp *const nets[2] = {a->policy_net, a->value_net};
+  for (int b = 0; b < 2; b++)
+    if (nets[b]->device_id != e.device_id || nets[b]->obs_dim != D || nets[b]->out_dim != kUpdOut[b])
+      return fail(SKYJO_E_INVALID, name + ": the nets must live on the engine's device, take the engine's observation and have 26 outputs and 1");
+  const bool kl = a->behaviour != nullptr;
+  const bool clipping = a->max_grad_norm > 0.f;  // (<= 0 and NaN: no clipping; +inf: measure only)
+  const UpdLayout u = upd_layout(D, count, mb, kl);
+  if (workspace_bytes < (int64_t)u.total) return fail(SKYJO_E_INVALID, name + ": workspace is smaller than skyjo_vec_ppo_update_workspace_bytes");
+  uint8_t *const w = (uint8_t *)workspace;
+  auto F = [&](size_t off) { return (float *)(w + off); };
+  int64_t *const ws_order = (int64_t *)(w + u.order), *const ws_fault = (int64_t *)(w + u.fault);
+  double *const loss_stats = (double *)(w + u.loss_stats);
+  float *const pair = F(u.pair);
+  float *const *const params[2] = {a->policy_params, a->value_params};
+  void *const state[2] = {a->policy_state, a->value_state};
+  const int64_t state_bytes[2] = {a->policy_state_bytes, a->value_state_bytes};
+  float *grads[2][SKU_TENSORS];
+  const float *twelve[2 * SKU_TENSORS];
+  int64_t counts[2 * SKU_TENSORS];
+  for (int b = 0; b < 2; b++)
+    for (int i = 0; i < SKU_TENSORS; i++) {
+      grads[b][i] = F(u.grads[b][i]);
+      twelve[b * SKU_TENSORS + i] = grads[b][i], counts[b * SKU_TENSORS + i] = (int64_t)sku_tensor_elems(i, D, kUpdOut[b]);
+    }
+  // the selection and the schedule
+  const int64_t *const order0 = a->orders ? a->orders : ws_order;
+  if (!a->orders)
+    if (int rc = shuffle_check(who, a->index, count, ws_order, ws_fault)) return rc;
+  SkGatherArgs gather{};
+  if (int rc = gather_check(who, h, a->records, a->layout, a->T, order0, std::min(mb, count), a->actions, a->logp, a->values, a->value_stride,
+                            a->advantages, a->value_targets, a->adv_mean, a->adv_std, F(u.obs), F(u.logmask), (int64_t *)(w + u.actions), F(u.logp),
+                            F(u.adv), F(u.vt), F(u.val), w + u.seats, gather))
+    return rc;
+  if (kl)
+    if (int rc = gather_logits_check(who, a->behaviour, n_rows, order0, std::min(mb, count), F(u.old_logits))) return rc;
+  // the optimiser: both branches' Adam at the first step (a later step changes the scalars alone) and the norm over the twelve gradients
+  SkUpdArgs adam[2];
+  SkNormArgs norm{};
+  for (int b = 0; b < 2; b++) {
+    adam[b] = SkUpdArgs{};
+    if (int rc = adam_check(who, nets[b], params[b], grads[b], state[b], state_bytes[b], a->lr, a->beta1, a->beta2, a->eps, a->first_step,
+                            clipping ? pair + 1 : nullptr, adam[b]))
+      return rc;
+  }
+  if (clipping)
+    if (int rc = grad_norm_check(who, twelve, counts, 2 * SKU_TENSORS, a->max_grad_norm, pair, norm)) return rc;
+  // the stages whose views depend on the row count: a full slice, and the short last one where count is no multiple of minibatch
+  const int64_t steps = (count + mb - 1) / mb, rows[2] = {std::min(mb, count), count % mb};
+  UpdSlice slice[2];
+  for (int k = 0; k < 2; k++) {
+    const int64_t m = rows[k];
+    if (m == 0) continue;  // (count == 0, or no short slice)
+    UpdSlice &sl = slice[k];
+    sl = UpdSlice{};
+    for (int b = 0; b < 2; b++) {
+      if (int rc = train_forward_check(who, D, kUpdOut[b], params[b], F(u.obs), m, F(u.out[b]), w + u.ws[b], u.ws_bytes[b], sl.fwd[b])) return rc;
+      if (int rc = train_backward_check(who, D, kUpdOut[b], params[b], F(u.obs), b == 0 ? F(u.g_logits) : F(u.g_value), m, grads[b], w + u.ws[b],
+                                        u.ws_bytes[b], sl.bwd[b]))
+        return rc;
+    }
+    if (int rc = ppo_loss_check(who, kl, F(u.out[0]), F(u.logmask), kl ? F(u.old_logits) : nullptr, F(u.out[1]), (const int64_t *)(w + u.actions),
+                                F(u.logp), F(u.adv), F(u.vt), F(u.val), m, a->clip, a->vf_coef, a->ent_coef, a->vf_clip, kl ? a->kl_coeff : 0.f,
+                                F(u.g_logits), F(u.g_value), loss_stats, w + u.loss_scratch, u.loss_scratch_bytes, sl.loss))
+      return rc;
+  }
+  // ---- the launches: nothing below allocates, copies to the host, synchronises or looks at device data ----
+  DevGuard guard_(e.device_id);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(epoch_stats_out, 0, (size_t)a->epochs * SKYJO_UPDATE_STATS * sizeof(double), s));
+  HIPCHK(hipMemsetAsync(fault_out, 0, sizeof(int64_t), s));
+  if (count == 0) return SKYJO_OK;
+  SkStatsArgs st{};
+  st.stats = loss_stats, st.pair = clipping ? pair : nullptr, st.acc = (double *)(w + u.acc);
+  st.epoch_fault = a->orders ? nullptr : (const long long *)ws_fault, st.fault_out = (long long *)fault_out;
+  st.inv_seen = 1.0 / (double)count, st.inv_steps = 1.0 / (double)steps, st.ns = kl ? SK_LOSS_KL_STATS : SK_LOSS_STATS;
+  int64_t step = a->first_step;
+  for (int32_t ep = 0; ep < a->epochs; ep++) {
+    const int64_t *order = a->orders ? a->orders + (size_t)ep * count : ws_order;
+    if (!a->orders)
+      if (int rc = shuffle_launch(a->index, count, a->seed, (uint32_t)ep, ws_order, ws_fault, s)) return rc;
+    for (int64_t k = 0; k < steps; k++, step++) {
+      const int64_t m = std::min(mb, count - k * mb);
+      const UpdSlice &sl = slice[m == rows[0] ? 0 : 1];
+      gather.index = (const long long *)(order + k * mb), gather.m = m;
+      if (int rc = gather_launch(gather, s)) return rc;
+      if (kl)
+        if (int rc = gather_logits_launch(a->behaviour, n_rows, order + k * mb, m, F(u.old_logits), s)) return rc;
+      for (int b = 0; b < 2; b++)
+        if (int rc = train_forward_launch(sl.fwd[b], s)) return rc;
+      if (int rc = ppo_loss_launch(kl, sl.loss, loss_stats, s)) return rc;
+      for (int b = 0; b < 2; b++)
+        if (int rc = train_backward_launch(sl.bwd[b], s)) return rc;
+      if (clipping)
+        if (int rc = grad_norm_launch(norm, s)) return rc;
+      for (int b = 0; b < 2; b++) {
+        adam_scalars(adam[b], a->lr, a->beta1, a->beta2, a->eps, step);
+        if (int rc = adam_launch(nets[b], adam[b], s)) return rc;
+      }
+      st.m = (double)m, st.first = k == 0, st.last = k == steps - 1, st.row = epoch_stats_out + (size_t)ep * SKYJO_UPDATE_STATS;
+      hipLaunchKernelGGL(k_update_stats, dim3(1), dim3(64), 0, s, st);
+      HIPCHK(hipGetLastError());
+    }
+  }
   return SKYJO_OK;
 }
 

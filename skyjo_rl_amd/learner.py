@@ -6,7 +6,8 @@ step itself: Adam fused with the re-pack of the updated weights into the ``Fused
 csrc/skyjo_update.h) - the rollout that follows needs no new nets - and with ``max_grad_norm`` RLlib's ``grad_clip`` in front of it: ``grad_norm``
 (``skyjo_vec_grad_norm``, csrc/skyjo_clip.h) takes the global norm of both branches' gradients and the step reads the coefficient from the
 device.  ``NativeBranch`` is what remains in between: one branch's forward, which keeps its activations, and its backward on the float32 master parameters (``skyjo_vec_mlp_train_forward`` / ``_backward``,
-csrc/skyjo_train.h: the exact float32 matrix instruction, no autograd graph, no allocation per step).
+csrc/skyjo_train.h: the exact float32 matrix instruction, no autograd graph, no allocation per step).  ``NativeUpdate`` queues all of it - every epoch and every
+minibatch step of an update, the shuffles and the epoch statistics included - behind ONE native call (``skyjo_vec_ppo_update``, csrc/skyjo_epoch.h).
 
 The definition (include/skyjo_vec.h has it in full): the masked softmax of ``action_mask_model.py:58-74`` - logits plus
 the log-mask - the clipped surrogate, the squared value error and the entropy of the PPO the reference trains with
@@ -344,6 +345,134 @@ class NativeAdam:
                 else:
                     _lib.check(self._L.skyjo_vec_mlp_adam_step(net._h, pp, gg, *hyper, stream))
         self.steps += 1
+
+
+UPDATE_STATS = STATS_KL + ("grad_norm", "grad_clipped", "rows")  # the columns of a row of ``NativeUpdate.run``'s statistics
+
+
+class NativeUpdate:
+    """A whole PPO update behind ONE native call (``skyjo_vec_ppo_update``): ``epochs`` passes over a selection in shuffled slices of
+    ``minibatch`` rows, every slice the step ``examples/ppo.py::ppo_update(native_batches=True, native_loss=True, native_nets=True)``
+    makes with a ``NativeAdam`` - gather, both branches' forward, the loss head, both backwards, the global-norm clip, Adam with the
+    re-pack - queued launch by launch in the same order with the same arguments, so the parameters, the Adam state and both
+    ``FusedNet``s end with the same bits; what the host loop does besides (a dozen ctypes calls per step, ``torch.randperm`` and the
+    sums of the statistics per epoch) happens once, or on the device.
+
+    ``env``: the engine whose buffers are updated from; ``model`` with its packed ``policy_net`` / ``value_net`` and ``optimizer``, a
+    ``NativeAdam`` made on exactly these; ``max_count``: the largest selection a ``run`` may get; ``minibatch`` and ``epochs``: the
+    schedule; ``kl``: the runs carry the KL term (``buf.behaviour`` and ``kl_coeff``).  The workspace (``workspace``, uint8, of
+    ``workspace_bytes``: minibatch columns, activations, the twelve gradients, the order ...), the statistics and the fault word are
+    allocated here, once; ``run`` allocates nothing.  The gradients live in the workspace: the parameters' ``.grad`` are NOT touched -
+    neither read nor written nor set."""
+
+    def __init__(self, env, model, policy_net, value_net, optimizer, max_count, minibatch, epochs, kl=False):
+        self._L = _lib.load()
+        if not isinstance(optimizer, NativeAdam) or [b[0] for b in optimizer._branches] != [policy_net, value_net]:
+            raise ValueError("optimizer must be a NativeAdam made on policy_net and value_net")
+        for name, x in (("max_count", max_count), ("minibatch", minibatch), ("epochs", epochs)):
+            if isinstance(x, bool) or int(x) != x or x < (0 if name == "max_count" else 1):
+                raise ValueError(f"{name} must be an integer, at least {0 if name == 'max_count' else 1}")
+        self.env, self.model, self.policy_net, self.value_net, self.optimizer = env, model, policy_net, value_net, optimizer
+        self.max_count, self.minibatch, self.epochs, self.kl = int(max_count), int(minibatch), int(epochs), bool(kl)
+        self._parameters()
+        dev = torch.device("cuda", env.device_index)
+        self.workspace_bytes = int(self._L.skyjo_vec_ppo_update_workspace_bytes(env._h, self.max_count, self.minibatch, int(self.kl)))
+        if self.workspace_bytes <= 0:
+            raise ValueError("max_count or minibatch is out of range")
+        self.workspace = torch.empty((self.workspace_bytes,), dtype=torch.uint8, device=dev)
+        self.stats = torch.zeros((self.epochs, _lib.UPDATE_STATS), dtype=torch.float64, device=dev)
+        self.fault = torch.zeros((1,), dtype=torch.int64, device=dev)
+
+    def _parameters(self):
+        """Both branches' six parameters as they are now, checked as ``FusedNet.branch_parameters`` and ``NativeBranch`` check them."""
+        if not self.policy_net._h or not self.value_net._h:
+            raise ValueError("a FusedNet of this update is closed")
+        dev = torch.device("cuda", self.env.device_index)
+        out = []
+        for seq, net, (_, mine, _, _) in zip((self.model.policy, self.model.value), (self.policy_net, self.value_net), self.optimizer._branches):
+            params = net.branch_parameters(seq)
+            if net.device != self.env.device_index or any(p.device != dev for p in params):
+                raise ValueError("the nets and the parameters must live on the engine's GPU")
+            if any(p is not q for p, q in zip(params, mine)):
+                raise ValueError("a parameter was replaced since the optimizer was made: its Adam state belongs to the old tensor")
+            if params[2].data_ptr() % 16 or params[4].data_ptr() % 16:
+                raise ValueError("linear 1.weight and 2.weight must start on a 16-byte boundary")
+            out.append(params)
+        return out
+
+    @torch.no_grad()
+    def run(self, buf, sel, *, seed, clip, vf_coef, ent_coef, vf_clip, kl_coeff=None, grad_clip=None, orders=None):
+        """One update on the rows ``sel`` (``rollout.select_rows(buf, ...)``) of ``buf`` (``rollout.compute_targets`` must have run; with
+        ``kl`` also ``rollout.behaviour_logits``): the one native call.  Returns ``(stats, fault)`` WITHOUT reading them - ``stats``
+        float64 [epochs, 10] on the device, a row per epoch in the order of ``UPDATE_STATS``: the head's six statistics and ``action_kl``
+        (0.0 without ``kl``) as row-weighted means, ``grad_norm`` and ``grad_clipped`` as means over the epoch's steps (0.0 without
+        ``grad_clip``) and the rows seen; ``fault`` int64 [1]: the shuffles' capped walks, 0 unless a kernel has a bug.  Both are this
+        object's tensors, refilled by the next ``run``.  The advantages are normalised with ``(sel.mean, max(sel.std, 1e-6))``.  Epoch e
+        is shuffled with ``rollout.epoch_order(sel, seed, e)``'s permutation, or is ``orders[e]`` where ``orders`` (int64
+        [epochs, count] on the device) is given.  ``lr`` / ``betas`` / ``eps`` are read from the optimizer now; its ``steps`` advance by
+        the steps queued, epochs x ceil(count / minibatch).  ``grad_clip``: None - no clipping; a number > 0 - RLlib's ``grad_clip``, as
+        ``NativeAdam.max_grad_norm``; inf - measure only.  The parameters' ``.grad`` are not touched.  ``ValueError``, before any
+        launch, for whatever the C side would refuse and for a closed net, a replaced parameter, ``sel.count > max_count`` or a buffer of
+        another engine."""
+        from . import rollout
+
+        if getattr(buf, "_env", None) is not self.env:
+            raise ValueError("buf belongs to another engine")
+        if getattr(buf, "advantages", None) is None:
+            raise ValueError("run needs the columns of compute_targets(buf)")
+        rollout._check_records(buf)
+        dev = buf.actions.device
+        count = int(sel.count)
+        if count > self.max_count:
+            raise ValueError(f"sel.count = {count} exceeds max_count = {self.max_count}")
+        rollout._check_index(buf, sel.index, tensor=True)
+        if sel.index.numel() != count or not sel.index.is_contiguous():
+            raise ValueError("sel.index must be contiguous and hold sel.count entries")
+        if self.kl != (kl_coeff is not None):
+            raise ValueError("kl_coeff belongs to kl=True, and kl=True needs it")
+        behaviour = None
+        if self.kl:
+            behaviour = getattr(buf, "behaviour", None)
+            if behaviour is None:
+                raise ValueError("kl=True needs the column of behaviour_logits(buf, policy_net)")
+            _column("buf.behaviour", behaviour, torch.float32, (buf.T, buf.B, NUM_ACTIONS), dev)
+            if not (math.isfinite(float(kl_coeff)) and float(kl_coeff) >= 0.0):
+                raise ValueError("kl_coeff must be finite and not negative")
+        if not (math.isfinite(float(clip)) and float(clip) > 0.0):
+            raise ValueError("clip must be finite and greater than 0")
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 1 << 64:
+            raise ValueError("seed must be an integer in 0 .. 2^64 - 1")
+        max_norm = 0.0 if grad_clip is None else _max_norm("grad_clip", grad_clip)
+        if orders is not None:
+            _column("orders", orders, torch.int64, (self.epochs, count), dev)
+        policy, value = self._parameters()
+        opt = self.optimizer
+        a = _lib.PPOUpdateArgs()
+        vp = lambda t: t.data_ptr()
+        a.records, a.actions, a.logp, a.values = vp(buf.records), vp(buf.actions), vp(buf.logp), vp(buf.values)
+        a.advantages, a.value_targets = vp(buf.advantages), vp(buf.value_targets)
+        a.behaviour = None if behaviour is None else vp(behaviour)
+        a.index = vp(sel.index) if count else vp(self.workspace)  # (an empty index has no address to pass; nothing reads it)
+        a.orders = None if orders is None or count == 0 else vp(orders)
+        a.policy_net, a.value_net = self.policy_net._h, self.value_net._h
+        a.policy_params, a.value_params = (C.c_void_p * 6)(*map(vp, policy)), (C.c_void_p * 6)(*map(vp, value))
+        (_, _, pstate, _), (_, _, vstate, _) = opt._branches
+        a.policy_state, a.value_state, a.policy_state_bytes, a.value_state_bytes = vp(pstate), vp(vstate), pstate.numel() * 4, vstate.numel() * 4
+        a.count, a.minibatch, a.first_step, a.seed = count, self.minibatch, opt.steps + 1, int(seed)
+        a.layout, a.T, a.value_stride, a.epochs = rollout._layout(buf), buf.T, buf.values.shape[-1], self.epochs
+        a.adv_mean, a.adv_std = float(sel.mean), float(max(sel.std, 1e-6))
+        a.clip, a.vf_coef, a.ent_coef = float(clip), float(vf_coef), float(ent_coef)
+        a.vf_clip = 0.0 if vf_clip is None or not math.isfinite(float(vf_clip)) or float(vf_clip) <= 0.0 else float(vf_clip)
+        a.kl_coeff = float(kl_coeff) if self.kl else 0.0
+        a.lr, a.beta1, a.beta2, a.eps, a.max_grad_norm = float(opt.lr), opt.betas[0], opt.betas[1], opt.eps, max_norm
+        with torch.cuda.device(dev):
+            rc = self._L.skyjo_vec_ppo_update(self.env._h, C.byref(a), vp(self.workspace), self.workspace_bytes, vp(self.stats), vp(self.fault),
+                                              torch.cuda.current_stream(dev).cuda_stream)
+        if rc == _lib.E_INVALID:  # (the C side checks everything before its first launch)
+            raise ValueError(self._L.skyjo_vec_last_error().decode())
+        _lib.check(rc)
+        opt.steps += self.epochs * -(-count // self.minibatch)
+        return self.stats, self.fault
 
 
 class _BranchFunction(torch.autograd.Function):

@@ -16,7 +16,8 @@ Where every seat trains a policy of its own (``arena.collect`` fills the same bu
 ``select_rows`` / ``minibatches`` take ``seats``: the rows in which those seats acted, with the moments of their advantages alone
 (``skyjo_vec_rollout_select_seats``).  ``behaviour_logits`` adds the one column the KL penalty of RLlib's PPO loss needs and the
 rollout does not record - the behaviour policy's logits per row -, ``gather_behaviour`` / ``minibatches(behaviour=True)`` hand its rows
-to ``learner.ppo_loss_kl`` (``skyjo_vec_rollout_gather_logits``).
+to ``learner.ppo_loss_kl`` (``skyjo_vec_rollout_gather_logits``).  ``epoch_order`` is an epoch's shuffle without torch: a keyed bijection evaluated on
+the device (``skyjo_vec_rollout_shuffle``), which ``minibatches(order=...)`` takes in place of its ``randperm``.
 """
 import ctypes as C
 import math
@@ -301,10 +302,49 @@ def gather_behaviour(buf, index, out=None):
     return out[:m]
 
 
-def minibatches(buf, size, generator=None, normalize=True, require=_lib.TGT_HAS_TARGET, selection=None, seats=None, behaviour=False):
+@torch.no_grad()
+def epoch_order(sel, seed, epoch, out=None):
+    """The selection ``sel`` (a ``Selection``) in the shuffled order of ``(seed, epoch)``, one native call that needs no torch generator
+    (``skyjo_vec_rollout_shuffle``, csrc/skyjo_epoch.h): returns ``(order, fault)`` - ``order`` int64 [count] with
+    ``order[j] = sel.index[perm(j)]``, ``perm`` a keyed bijection of [0, count) that is a pure function of ``(count, seed, epoch, j)``
+    (include/skyjo_vec.h has it; tests/epoch_order_ref.py restates it), and ``fault`` int64 [1] ON THE DEVICE: the number of positions
+    whose walk hit its cap and hold -1 (a row of zeros to ``gather_rows``) - 0 unless the kernel has a bug; read it when you read your
+    other statistics.  Nothing is read back here: no synchronisation.  ``seed``: 0 .. 2^64 - 1, ``epoch``: 0 .. 2^32 - 1.  ``out``: a
+    contiguous int64 tensor of at least count entries on the index's device, not overlapping it, to refill; its first count entries
+    are returned.  What ``minibatches(order=...)`` takes, and what ``skyjo_vec_ppo_update`` does per epoch by itself."""
+    index, count = sel.index, int(sel.count)
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1 or index.device.type != "cuda" or not index.is_contiguous():
+        raise ValueError("sel.index must be a contiguous one-dimensional int64 tensor on a GPU")
+    if index.numel() != count:
+        raise ValueError("sel.index does not hold sel.count entries")
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 1 << 64:
+        raise ValueError("seed must be an integer in 0 .. 2^64 - 1")
+    if isinstance(epoch, bool) or int(epoch) != epoch or not 0 <= int(epoch) < 1 << 32:
+        raise ValueError("epoch must be an integer in 0 .. 2^32 - 1")
+    dev = index.device
+    if out is None:
+        out = torch.empty((count,), dtype=torch.int64, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or out.dim() != 1 or out.numel() < count or out.device != dev
+          or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous one-dimensional int64 tensor of at least count entries on the index's device")
+    fault = torch.zeros((1,), dtype=torch.int64, device=dev)
+    if count == 0:  # (an empty index has no address to pass)
+        return out[:0], fault
+    with torch.cuda.device(dev):
+        rc = _lib.load().skyjo_vec_rollout_shuffle(index.data_ptr(), count, int(seed), int(epoch), out.data_ptr(), fault.data_ptr(),
+                                                   torch.cuda.current_stream(dev).cuda_stream)
+    if rc == _lib.E_INVALID:
+        raise ValueError(_lib.load().skyjo_vec_last_error().decode())
+    _lib.check(rc)
+    return out[:count], fault
+
+
+def minibatches(buf, size, generator=None, normalize=True, require=_lib.TGT_HAS_TARGET, selection=None, seats=None, order=None, behaviour=False):
     """One epoch over the selected rows in shuffled minibatches: ``select_rows`` (or a ``selection`` made earlier), a
     ``torch.randperm`` of it (``generator``: a generator on the buffer's device), and ``gather_rows`` per slice of ``size`` rows into
     ONE ``Minibatch`` that every step refills - use a batch before asking for the next.  The last slice may be short.
+    ``order``: the epoch's shuffled index itself, int64 [count] on the buffer's device (``epoch_order(selection, seed, epoch)``), taken
+    instead of the ``randperm`` draw - the generator is not touched; None: everything as described.
     ``normalize``: True - the selection's (mean, std), a std of 0 counting as 1; ``(mean, std)``; or None / False.  ``seats``: as for
     ``select_rows`` - the rows of these seats only, normalised with their own moments (``ValueError`` next to a ``selection``, which
     has chosen its rows already).  ``behaviour``: True - every step yields ``(minibatch, old_logits)``, ``old_logits`` float32 [m, 26] the
@@ -318,7 +358,13 @@ def minibatches(buf, size, generator=None, normalize=True, require=_lib.TGT_HAS_
         normalize = (sel.mean, sel.std if sel.std > 0.0 else 1.0)
     elif normalize is False:
         normalize = None
-    perm = sel.index[torch.randperm(sel.count, device=sel.index.device, generator=generator)]
+    if order is None:
+        perm = sel.index[torch.randperm(sel.count, device=sel.index.device, generator=generator)]
+    else:
+        _check_index(buf, order, tensor=True)
+        if order.numel() != sel.count:
+            raise ValueError(f"order holds {order.numel()} entries, the selection {sel.count}")
+        perm = order
     out = new_minibatch(buf, min(size, sel.count))
     old = torch.empty((out.actions.shape[0], 26), dtype=torch.float32, device=sel.index.device) if behaviour else None
     for k in range(0, sel.count, size):
