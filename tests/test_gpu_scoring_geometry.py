@@ -256,12 +256,13 @@ def test_one_launch_plays_every_game_to_its_end(N, ind):
 
 
 # ----------------------------------------------------------------------------------------------------------------- 4. caller actions
-def caller_actions(rng, mask, n):
-    """One step's actions: a uniformly random legal action per game, 0.2 % arbitrary ones from -2 .. 28 (mostly illegal), 1 % SKYJO_ACTION_SKIP."""
+def caller_actions(rng, mask, n, share=0.002):
+    """One step's actions: a uniformly random legal action per game, 0.2 % (``share``) arbitrary ones from -2 .. 28 (mostly illegal),
+    1 % SKYJO_ACTION_SKIP."""
     from oracle import skyjo_oracle as so
 
     acts = np.argmax(rng.random((n, 26)) * mask, axis=1).astype(np.int32)
-    bad = rng.random(n) < 0.002
+    bad = rng.random(n) < share
     acts[bad] = rng.integers(-2, 29, size=int(bad.sum()))
     acts[rng.random(n) < 0.01] = so.ACTION_SKIP
     return acts
