@@ -14,6 +14,7 @@
 
 #include "skyjo_device.h"
 #include "skyjo_host.h"
+#include "skyjo_deal_schedule.h"
 
 // Measurement switches (environment variables: tools/dev/README.md) exist in -DSK_DIAG builds only; the shipped library reads no
 // environment variable at all - what a caller or a test may choose is an option of skyjo_vec_set_option.
@@ -37,7 +38,6 @@ std::atomic<uint64_t> g_generation{0};
 
 #define GUARD(h) DevGuard guard_((h)->cfg.device_id)
 
-constexpr int kMaxRolloutChunk = 128;  // lockstep iterations per k_step launch (the tile stays in LDS for a whole launch)
 constexpr int kMaxCyclesPerLaunch = 16;  // k_cycle: whole dealing cycles per launch (each of deal_every_iters iterations)
 constexpr size_t kCuLds = 160 * 1024;    // a compute unit's LDS: what a k_cycle workgroup may fill
 
@@ -60,14 +60,6 @@ struct DealRequests {
   int cycle_s = 0;   // SKYJO_OPT_CYCLE_S (0: the batch's share)
 };
 
-// The dealing run that has been started and not yet published.
-enum class InFlight {
-  None,
-  ListRun,  // a work-list run on deal_stream: k_publish makes its episodes available
-  Planned,  // a run the step kernel planned, waiting for the k_cycle launch that carries it (inflight_tag: its id)
-  Dealing   // a planned run that is being dealt or has been: the next step kernel publishes it, or k_publish_all
-};
-
 // k_deal's third argument: where the run's games come from and who publishes its episodes
 enum class DealRun : int {
   ListBeside = 0,  // the work list; k_publish follows
@@ -75,6 +67,7 @@ enum class DealRun : int {
   ScanInline = 2,  // lane = game, own scan; k_deal publishes
   Planned = 3      // lane = game, planned by the step kernel, which also publishes
 };
+
 // Default number of lockstep iterations between two dealing runs.  A run adds one episode to every bank that is not
 // full, so the interval has to stay below the mean episode length of the policy in use (random admissible policy:
 // 76 / 105 / 134 steps for 2 / 3 / 4 players) or the banks of SK_BANK episodes drain and finished games deal in
@@ -105,41 +98,35 @@ constexpr int deal_interval_default(int num_players, DealForm form, int cycle_s)
 }  // namespace
 
 struct skyjo_vec {
+  // ---- identity and what persists of the kernels' arguments (a launch sets its per-launch words on a copy of P) ----
   uint64_t generation = 0;  // unique per created handle in this process (snapshots remember it)
   skyjo_vec_config cfg{};
   SkParams P{};
   size_t G = 0;           // tiles * 64
+  bool seeded = false;
+  uint64_t iter = 0;        // rollout iterations (the policy's Philox counter)
+  uint64_t iters_total = 0; // lockstep iterations of any kind since the counters were reset
+  uint32_t *health_host = nullptr;  // host side of P.health_host
+  int ncu = 256;            // compute units of the device (k_cycle's workgroup sizing)
   size_t lds_bytes = 0, lds_tile = 0;
   size_t lds_rollout = 0, lds_step = 0;  // the step kernels of 2 / 3 / 4 players keep their statistics in registers: smaller footprints (fused rollout / caller actions)
-  bool seeded = false;
-  int pending_iters = 0;  // lockstep iterations since the dealing kernel last ran
-  int deal_every_iters = 64;  // (resolve_form sets it with interval_default)
-  // The interval adapts itself unless it was set explicitly: every dealing run reports how many banks it found empty
-  // (host-mapped word, no synchronisation); any empty bank shortens the interval, a long calm stretch lengthens it
-  // back towards the default.  Results never depend on the cadence (tests/test_gpu_parity.py), only the speed does.
-  bool auto_interval = true;
-  int interval_default = 64, calm_runs = 0;
-  uint32_t health_seen = 0;
-  uint32_t *health_host = nullptr;
-  // the dealing form: requests -> resolve_form() -> form and, for k_cycle, its workgroup shape
+  // ---- the dealing form: requests -> resolve_form() -> form and, for k_cycle, its workgroup shape ----
   DealRequests req;
   DealForm form = DealForm::InlineScan;
   bool one_kernel_capable = false;  // two to four players and k_cycle may use a whole CU's LDS
   int cycle_s = SK_CYCLE_MAX_S;     // step (= dealing) wavefronts per workgroup of k_cycle
   size_t lds_cycle = 0, lds_cycle_step = 0;  // k_cycle's dynamic LDS and one step wavefront's region in it, for the record layout in force
   uint32_t cycle_deal_arg = 0;      // k_cycle's lds_deal_bytes argument: a dealing wavefront's region | the flag bits (skyjo_cycle.h)
+  int max_cycles = 0;       // SKYJO_OPT_MAX_CYCLES_PER_LAUNCH (0: the ABI's maximum, kMaxCyclesPerLaunch)
   hipStream_t deal_stream = nullptr;  // k_deal's stream in the two-stream forms
   hipEvent_t ev_scan = nullptr, ev_dealt = nullptr;
-  InFlight inflight = InFlight::None;
-  uint32_t inflight_tag = 0;
-  int list_sel = 0;
-  uint32_t deal_tag = 0;  // k_step launches between two k_deal launches inside skyjo_vec_rollout
-  uint64_t iter = 0;        // rollout iterations (the policy's Philox counter)
-  uint64_t iters_total = 0; // lockstep iterations of any kind since the counters were reset
-  // Small batches (single-game views): the *_host conveniences go through host-mapped memory - the kernel reads the actions
-  // from it and writes the records AND every game's packed state, rewards and scores to it (sk_export_raw), so a call is one
-  // launch + one stream synchronisation, and skyjo_vec_get_state / get_rewards_host afterwards are served from `hm_raw`
-  // (raw_valid) without touching the device.
+  DealSchedule deal;  // the dealing schedule
+  bool rec_planar_all = false;  // ... = SKYJO_REC_TILE_PLANAR_ALL: reset / observe / step / step_collect / model_rollout write their records tile-planar as well
+  bool rec_planar = false;  // SKYJO_OPT_RECORD_LAYOUT: skyjo_vec_rollout writes its records tile-planar (one-kernel form, either observation)
+  // ---- the host channel of the *_host conveniences (host_bufs) ----
+  // Small batches (single-game views) go through host-mapped memory - the kernel reads the actions from it and writes the records
+  // AND every game's packed state, rewards and scores to it (sk_export_raw), so a call is one launch + one stream synchronisation,
+  // and skyjo_vec_get_state / get_rewards_host afterwards are served from `hm_raw` (raw_valid) without touching the device.
   bool fast_host = false, raw_valid = false;
   bool host_spin = true;    // single-tile engines: spin on the kernel's sign-off word (SKYJO_NO_SPIN=1 at create time: synchronise the stream)
   bool raw_export = false;  // the kernel also writes every game's packed state to host-mapped memory (few tiles only, see skyjo_vec_create)
@@ -150,19 +137,15 @@ struct skyjo_vec {
   uint8_t *hm_mask_d = nullptr, *hm_records_d = nullptr, *hm_raw_d = nullptr;
   int raw_stride = 0;
   uint32_t host_seq = 0;  // sequence number of the last host-style step of a single-tile engine (see skyjo_vec_step_host)
-  uint32_t cycle_seq = 0;   // k_cycle launches so far: launch L counts empty banks into bank_empty[L & 1] and reports the other word
-  int ncu = 256;            // compute units of the device (k_cycle's workgroup sizing)
-  int max_cycles = 0;       // SKYJO_OPT_MAX_CYCLES_PER_LAUNCH (0: the ABI's maximum, kMaxCyclesPerLaunch)
-  bool rec_planar_all = false;  // ... = SKYJO_REC_TILE_PLANAR_ALL: reset / observe / step / step_collect / model_rollout write their records tile-planar as well
-  bool rec_planar = false;  // SKYJO_OPT_RECORD_LAYOUT: skyjo_vec_rollout writes its records tile-planar (one-kernel form, either observation)
-  // lazily allocated scratch for the *_host conveniences
+  // larger batches are staged through device scratch, allocated when the first such call needs it
   int32_t *d_actions = nullptr;
   uint8_t *d_records = nullptr;
   uint8_t *d_mask = nullptr;
-  // skyjo_vec_rollout_select's scratch (sk_engine_select_scratch: allocated on first use, grown when a call needs more).  Not part
-  // of a snapshot.
+  // ---- skyjo_vec_rollout_select's scratch (sk_engine_select_scratch: allocated on first use, grown when a call needs more).  Not
+  // part of a snapshot. ----
   void *sel_scratch = nullptr;
   size_t sel_blocks = 0;
+  // ---- the arena allocator (dalloc) ----
   std::vector<std::pair<void *, size_t>> allocs;  // every device array of the handle with its size (snapshots copy them all)
   // The arrays made at create time are carved out of ONE allocation, the large ones at 2 MB boundaries: how the generator
   // states, the banks and the live tiles lie relative to each other in the memory channels is then the same in every
@@ -172,7 +155,7 @@ struct skyjo_vec {
   uint8_t *arena = nullptr;
   size_t arena_off = 0;
   int arena_mode = 0;  // 1: adding up, 2: carving
-  // optional per-launch timing with HIP events on the launch stream (bench.py roofline leg)
+  // ---- optional per-launch timing with HIP events on the launch stream (bench.py roofline leg) ----
   bool profile = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[SKYJO_PROF_KERNELS];  // k_step, k_scan, k_deal, k_publish, k_net_*
 };
@@ -185,9 +168,8 @@ struct skyjo_vec_snapshot {
   void *blob = nullptr;
   size_t bytes = 0;
   // host side of the engine's state
-  int pending_iters = 0, deal_every_iters = 0, calm_runs = 0, list_sel = 0;
-  bool auto_interval = true;
-  uint32_t health_seen = 0, deal_tag = 0, health[2] = {0, 0};
+  DealState deal;
+  uint32_t health[2] = {0, 0};
   uint64_t iter = 0, iters_total = 0;
 };
 
@@ -282,16 +264,22 @@ constexpr KernelRow<decltype(&k_step<true, true, 2>)> kStepKernels[] = {SK_ROW(t
 #undef SK_ROWS
 #undef SK_ROW
 
-// `be_read`: the bank_empty word the run reports (default: the run's own parity, as the step kernel that planned it counted)
-int launch_deal_kernel(skyjo_vec *h, hipStream_t ds, DealRun run, int be_read = -1) {
+// ---- the dealing schedule: the only code that reads or writes h->deal and the kernels' per-launch dealing words.  What the entry
+// points use: deals_drain, deals_refill, deals_plan_launch / deals_enter_launch (through launch_step) / deals_finish_launch, and
+// the interval's accessors ----
+
+// `tag`: the run's id; `be_read`: the bank_empty word the run reports (a run of the latest id: the word of its own parity, as the step
+// kernel that planned it counted)
+int launch_deal_kernel(skyjo_vec *h, hipStream_t ds, DealRun run, uint32_t tag, uint32_t be_read) {
   hipEvent_t e0, e1;
   int rc;
-  h->P.be_read = be_read >= 0 ? (uint32_t)be_read : (h->P.deal_tag & 1u);
+  SkParams P = h->P;
+  P.deal_tag = tag, P.be_read = be_read;
   if ((rc = prof_events(h, 2, &e0, &e1))) return rc;
-  const int np = fixed_players(h->P.L.N);
+  const int np = fixed_players(P.L.N);
   // fixed player counts deal from a byte deck per lane; the generic kernel needs the tile + ring
-  hipExtLaunchKernelGGL(find_kernel(kDealKernels, kernel_key(np)), dim3(h->P.tiles), dim3(SK_TILE), np ? kDealLds : (uint32_t)(h->lds_tile + 16384), ds, e0, e1, 0, h->P,
-                        h->list_sel, (int)run);
+  hipExtLaunchKernelGGL(find_kernel(kDealKernels, kernel_key(np)), dim3(P.tiles), dim3(SK_TILE), np ? kDealLds : (uint32_t)(h->lds_tile + 16384), ds, e0, e1, 0, P,
+                        h->deal.st.list_sel, (int)run);
   HIPCHK(hipGetLastError());
   return SKYJO_OK;
 }
@@ -299,74 +287,73 @@ int launch_deal_kernel(skyjo_vec *h, hipStream_t ds, DealRun run, int be_read = 
 // Planned -> Dealing without the k_cycle launch that should have carried the run (the caller went on with another kind of call):
 // the dealing kernel alone, on the caller's stream.
 int flush_planned(skyjo_vec *h, hipStream_t s) {
-  if (h->inflight != InFlight::Planned) return SKYJO_OK;
-  const uint32_t keep = h->P.deal_tag;
-  h->P.deal_tag = h->inflight_tag;
-  h->inflight = InFlight::Dealing;
-  const int rc = launch_deal_kernel(h, s, DealRun::Planned, (int)((h->cycle_seq - 1u) & 1u));  // (the word the k_cycle launch that planned it counted into)
-  h->P.deal_tag = keep;
-  return rc;
+  DealSchedule &d = h->deal;
+  if (d.inflight != InFlight::Planned) return SKYJO_OK;
+  d.inflight = InFlight::Dealing;
+  return launch_deal_kernel(h, s, DealRun::Planned, d.inflight_tag, (d.cycle_seq - 1u) & 1u);  // (the word the k_cycle launch that planned it counted into)
 }
 
 // Any state -> None: the episodes of the run in flight become available on stream `s`.
-int publish_deals(skyjo_vec *h, hipStream_t s) {
+int deals_drain(skyjo_vec *h, hipStream_t s) {
+  DealSchedule &d = h->deal;
   int rc = flush_planned(h, s);
   if (rc) return rc;
-  if (h->inflight == InFlight::None) return SKYJO_OK;
+  if (d.inflight == InFlight::None) return SKYJO_OK;
   if (uses_deal_stream(h->form)) HIPCHK(hipStreamWaitEvent(s, h->ev_dealt, 0));
   hipEvent_t e0, e1;
   if ((rc = prof_events(h, 3, &e0, &e1))) return rc;
-  if (h->inflight == InFlight::ListRun) {
-    hipExtLaunchKernelGGL(k_publish, dim3(64), dim3(256), 0, s, e0, e1, 0, h->P, h->list_sel);
+  if (d.inflight == InFlight::ListRun) {
+    hipExtLaunchKernelGGL(k_publish, dim3(64), dim3(256), 0, s, e0, e1, 0, h->P, d.st.list_sel);
   } else {
     const int G = h->P.tiles * SK_TILE;
     hipExtLaunchKernelGGL(k_publish_all, dim3((G + 255) / 256), dim3(256), 0, s, e0, e1, 0, h->P);
   }
   HIPCHK(hipGetLastError());
-  h->inflight = InFlight::None;
+  d.inflight = InFlight::None;
   return SKYJO_OK;
 }
 
 static void adapt_interval(skyjo_vec *h) {
-  if (h->auto_interval) {
-    const volatile uint32_t *hh = h->health_host;
-    const uint32_t tag = hh[1], empty = hh[0];
-    if (tag != h->health_seen) {  // the report of a run that has finished since the last look (one or two runs old)
-      h->health_seen = tag;
-      // An empty bank at scan time is a warning (one more game end before the next run deals in place), not yet a
-      // stall: a handful of them is tolerated, one game in a thousand is not.
-      const uint32_t many = (uint32_t)(h->P.B / 1024 > 1 ? h->P.B / 1024 : 1);
-      if (empty >= many) {
-        const int cut = h->deal_every_iters / 8 > 4 ? h->deal_every_iters / 8 : 4;
-        h->deal_every_iters = h->deal_every_iters - cut > 8 ? h->deal_every_iters - cut : 8;
-        h->calm_runs = 0;
-      } else if (empty) {
-        h->calm_runs = 0;
-      } else if (++h->calm_runs >= 8 && h->deal_every_iters < h->interval_default) {
-        h->deal_every_iters += 2;
-        h->calm_runs = 0;
-      }
-    }
+  DealState &st = h->deal.st;
+  const volatile uint32_t *hh = h->health_host;
+  const uint32_t tag = hh[1], empty = hh[0];
+  if (!st.auto_interval || tag == st.health_seen) return;
+  st.health_seen = tag;  // the report of a run that has finished since the last look (one or two runs old)
+  // An empty bank at scan time is a warning (one more game end before the next run deals in place), not yet a
+  // stall: a handful of them is tolerated, one game in a thousand is not.
+  const uint32_t many = (uint32_t)(h->P.B / 1024 > 1 ? h->P.B / 1024 : 1);
+  if (empty >= many) {
+    const int cut = st.deal_every_iters / 8 > 4 ? st.deal_every_iters / 8 : 4;
+    st.deal_every_iters = st.deal_every_iters - cut > 8 ? st.deal_every_iters - cut : 8;
+    st.calm_runs = 0;
+  } else if (empty) {
+    st.calm_runs = 0;
+  } else if (++st.calm_runs >= 8 && st.deal_every_iters < h->deal.interval_default) {
+    st.deal_every_iters += 2;
+    st.calm_runs = 0;
   }
 }
-static void next_deal_tag(skyjo_vec *h, bool flip_list) {
-  if (flip_list) h->list_sel ^= 1;  // (the work lists alternate: k_publish of one run clears the other's counter)
-  h->deal_tag = (h->deal_tag + 1) & 0x7fffffffu;
-  if (h->deal_tag == 0) h->deal_tag = 1;
-  h->P.deal_tag = h->deal_tag;
+// the next run's id: it becomes the latest one, for the host and (P.deal_tag, which persists) for the kernels
+static uint32_t next_deal_tag(skyjo_vec *h, bool flip_list) {
+  DealState &st = h->deal.st;
+  if (flip_list) st.list_sel ^= 1;  // (the work lists alternate: k_publish of one run clears the other's counter)
+  st.deal_tag = (st.deal_tag + 1) & 0x7fffffffu;
+  if (st.deal_tag == 0) st.deal_tag = 1;
+  return h->P.deal_tag = st.deal_tag;
 }
 
 // One dealing run that the step kernel did not plan: publish the previous one, then deal one episode for every bank that is not
 // full.  In line (-> None) k_deal publishes its own episodes; in the two-stream forms (-> ListRun) it runs on deal_stream beside the
 // step launches that follow, and its episodes are published at the start of the next run, long before a bank of SK_BANK runs dry.
-// The forms that do not plan make every run this way; seeding and resets fill the banks this way in every form.
+// The forms that do not plan make every run this way; seeding and resets fill the banks this way in every form (deals_refill).
 int start_deals(skyjo_vec *h, hipStream_t s) {
+  DealSchedule &d = h->deal;
   int rc;
   if (h->req.no_bank) {  // nothing is ever dealt ahead: a reset deals in place (deal_inline)
-    h->pending_iters = 0;
+    d.st.pending_iters = 0;
     return SKYJO_OK;
   }
-  if ((rc = publish_deals(h, s))) return rc;
+  if ((rc = deals_drain(h, s))) return rc;
   adapt_interval(h);
   next_deal_tag(h, true);
   // In line, the dealing kernel looks at the banks itself (lane = game) unless the work list was asked for: no k_scan launch.  Beside
@@ -378,81 +365,123 @@ int start_deals(skyjo_vec *h, hipStream_t s) {
     hipEvent_t e0, e1;
     if ((rc = prof_events(h, 1, &e0, &e1))) return rc;
     hipExtLaunchKernelGGL(k_scan, dim3((h->P.B + SK_SCAN_BLOCK - 1) / SK_SCAN_BLOCK), dim3(SK_SCAN_BLOCK), 0, s, e0, e1, 0, h->P,
-                          h->list_sel);
+                          d.st.list_sel);
     HIPCHK(hipGetLastError());
   }
   if (beside) {
     HIPCHK(hipEventRecord(h->ev_scan, s));
     HIPCHK(hipStreamWaitEvent(h->deal_stream, h->ev_scan, 0));
   }
-  if ((rc = launch_deal_kernel(h, beside ? h->deal_stream : s, run))) return rc;
+  if ((rc = launch_deal_kernel(h, beside ? h->deal_stream : s, run, d.st.deal_tag, d.st.deal_tag & 1u))) return rc;
   if (beside) {
     HIPCHK(hipEventRecord(h->ev_dealt, h->deal_stream));
-    h->inflight = InFlight::ListRun;
+    d.inflight = InFlight::ListRun;
   }
-  h->pending_iters = 0;
+  d.st.pending_iters = 0;
   return SKYJO_OK;
 }
+// One run that nobody planned, then published: what was taken from the banks (a reset, a new seed) is there again on stream `s`.
+int deals_refill(skyjo_vec *h, hipStream_t s) {
+  const int rc = start_deals(h, s);
+  return rc ? rc : deals_drain(h, s);
+}
 
-// The pipelined protocol (skyjo_device.h, sk_plan_deals) of TwoStreamsPipelined and OneKernel: plan_cycle() before the step launch
-// after which the run is due - that launch plans the run on its way out -, start_deals_planned() after it.  Nothing on the caller's
-// stream waits.
+// The pipelined protocol (skyjo_device.h, sk_plan_deals) of TwoStreamsPipelined and OneKernel: the step launch after which the run
+// is due plans it on its way out (deals_plan_launch gives the run its id), start_deals_planned() follows the launch.  Nothing on the
+// caller's stream waits.
 bool plans_ahead(const skyjo_vec *h) {
   return (h->form == DealForm::TwoStreamsPipelined || h->form == DealForm::OneKernel) && !h->req.no_bank;
 }
-void plan_cycle(skyjo_vec *h) {
-  next_deal_tag(h, false);
-  h->P.plan_new_tag = h->deal_tag;
-  h->P.be_add = h->deal_tag & 1u;  // (a k_cycle launch overrides this with its launch parity: launch_step)
-  h->P.ov_flags |= 2u;
-}
 int start_deals_planned(skyjo_vec *h, hipStream_t s) {
+  DealSchedule &d = h->deal;
   int rc;
   if (h->form == DealForm::OneKernel) {  // -> Planned: the next k_cycle launch carries the run; nothing is launched here
     if ((rc = flush_planned(h, s))) return rc;  // (an older run that no launch has carried yet: deal it now)
-    h->inflight = InFlight::Planned, h->inflight_tag = h->deal_tag;
+    d.inflight = InFlight::Planned, d.inflight_tag = d.st.deal_tag;
   } else {  // -> Dealing: the dealing kernel goes to its own stream behind an event for the launch that planned the run
     HIPCHK(hipEventRecord(h->ev_scan, s));
     HIPCHK(hipStreamWaitEvent(h->deal_stream, h->ev_scan, 0));
-    if ((rc = launch_deal_kernel(h, h->deal_stream, DealRun::Planned))) return rc;
+    if ((rc = launch_deal_kernel(h, h->deal_stream, DealRun::Planned, d.st.deal_tag, d.st.deal_tag & 1u))) return rc;
     HIPCHK(hipEventRecord(h->ev_dealt, h->deal_stream));
-    h->inflight = InFlight::Dealing;
+    d.inflight = InFlight::Dealing;
   }
-  h->pending_iters = 0;
+  d.st.pending_iters = 0;
   adapt_interval(h);  // (for the cycles to come)
   return SKYJO_OK;
 }
-// the run that is due after a step launch, in the engine's form
-int start_due_deals(skyjo_vec *h, hipStream_t s) { return plans_ahead(h) ? start_deals_planned(h, s) : start_deals(h, s); }
 
-int launch_step(skyjo_vec *h, hipStream_t s, bool policy, const int32_t *actions, uint8_t *rec, int32_t *act_out,
-                int iters, uint64_t policy_seed, double *end_rew = nullptr, uint8_t *end_flag = nullptr, uint8_t *raw_out = nullptr,
-                int cycle_len = 0, bool planar_out = false) {
+// Plan a launch: how many of the `wanted` iterations the next step launch takes (plan_launch) and, where the form plans
+// ahead and a run is due after it, that run's id.  `fused`: a launch of the fused rollout - in the one-kernel form it keeps its
+// tiles in LDS over several dealing cycles when the caller asks for that many iterations at once: up to kMaxCyclesPerLaunch whole
+// cycles in ONE launch (the cycle ends inside it are handled by the kernel: step_body, k_cycle).
+// (Only where the kernel's cycle ends have a run to hand over: an engine that never deals ahead - SKYJO_OPT_NO_BANK - plans nothing,
+// and a cycle end inside its launch would publish and plan with a stale id: ADVICE r4)
+StepLaunch deals_plan_launch(skyjo_vec *h, int wanted, bool fused) {
+  const DealState &st = h->deal.st;
+  const bool planned = plans_ahead(h);
+  const int cap = h->max_cycles > 0 ? h->max_cycles : kMaxCyclesPerLaunch;
+  StepLaunch L{plan_launch(wanted, st.pending_iters, st.deal_every_iters, fused && planned && h->form == DealForm::OneKernel, cap), 0};
+  if (L.due && planned) {
+    L.plan_tag = next_deal_tag(h, false);  // the id of the first run planned by this launch; the kernel counts on from it
+    for (int c = 1; c < L.cycles; c++) next_deal_tag(h, false);
+  }
+  return L;
+}
+// The schedule's part in a step launch: the dealing words of `P`, the launch's copy of h->P.  A k_cycle launch (`cycle_kernel`)
+// carries the planned run, *carried = its id (0: none), Planned -> Dealing; in front of any other step kernel that run is dealt
+// now - it does not wait for a k_cycle launch.
+int deals_enter_launch(skyjo_vec *h, hipStream_t s, const StepLaunch &L, bool cycle_kernel, SkParams &P, uint32_t *carried) {
+  DealSchedule &d = h->deal;
+  if (d.inflight == InFlight::Planned || d.inflight == InFlight::Dealing) P.ov_flags |= 1u;  // publish what has been dealt since (sk_publish_deals)
+  if (L.plan_tag) P.ov_flags |= 2u, P.plan_new_tag = L.plan_tag, P.be_add = L.plan_tag & 1u;
+  *carried = 0;
+  if (!cycle_kernel) return flush_planned(h, s);
+  if (d.inflight == InFlight::Planned) *carried = d.inflight_tag, d.inflight = InFlight::Dealing;
+  P.be_add = d.cycle_seq & 1u, P.be_read = (d.cycle_seq & 1u) ^ 1u;  // (the launch's parity, not the run's)
+  d.cycle_seq++;
+  return SKYJO_OK;
+}
+// Finish a launch: its iterations count, and the run that fell due is started in the engine's form.
+int deals_finish_launch(skyjo_vec *h, hipStream_t s, const StepLaunch &L) {
+  h->deal.st.pending_iters += L.iters;
+  if (!L.due) return SKYJO_OK;
+  return plans_ahead(h) ? start_deals_planned(h, s) : start_deals(h, s);
+}
+
+// the interval: resolve_form's default for the form, an explicit value (SKYJO_OPT_DEAL_INTERVAL), the one in force
+void deals_set_interval_default(skyjo_vec *h, int iters) {
+  h->deal.interval_default = iters;
+  if (h->deal.st.auto_interval) h->deal.st.deal_every_iters = iters;
+}
+void deals_set_interval(skyjo_vec *h, int iters) { h->deal.st.deal_every_iters = iters, h->deal.st.auto_interval = false; }
+int deals_interval(const skyjo_vec *h) { return h->deal.st.deal_every_iters; }
+// ---- end of the dealing schedule ----
+
+// One step launch as deals_plan_launch sized it; deals_finish_launch follows it.  `host_seq`: see skyjo_vec_step_host.
+int launch_step(skyjo_vec *h, hipStream_t s, const StepLaunch &L, bool policy, const int32_t *actions, uint8_t *rec, int32_t *act_out,
+                uint64_t policy_seed, double *end_rew = nullptr, uint8_t *end_flag = nullptr, uint8_t *raw_out = nullptr,
+                bool planar_out = false, uint32_t host_seq = 0) {
   h->raw_valid = false;  // (the host's copy of the games is stale from here on; step_host sets it again)
-  const bool ind = h->P.L.indirect != 0;
+  SkParams P = h->P;     // the launch's own copy: the per-launch words are set here and nowhere put back
+  P.host_seq = host_seq;
+  const bool ind = P.L.indirect != 0;
+  // one kernel for the whole dealing cycle: S step + S dealing wavefronts per workgroup (= per CU)
+  const bool cycle_kernel = h->form == DealForm::OneKernel && policy && !end_rew && !raw_out;
   int rc;
   hipEvent_t e0, e1;
-  if ((rc = prof_events(h, 0, &e0, &e1))) return rc;
-  if (h->inflight == InFlight::Planned || h->inflight == InFlight::Dealing) h->P.ov_flags |= 1u;  // publish what has been dealt since (sk_publish_deals)
-  if (h->form == DealForm::OneKernel && policy && !end_rew && !raw_out) {
-    // one kernel for the whole dealing cycle: S step + S dealing wavefronts per workgroup (= per CU); Planned -> Dealing
-    uint32_t tag = 0;
-    if (h->inflight == InFlight::Planned) tag = h->inflight_tag, h->inflight = InFlight::Dealing;
-    h->P.be_add = h->cycle_seq & 1u, h->P.be_read = (h->cycle_seq & 1u) ^ 1u;
-    h->cycle_seq++;
+  uint32_t tag;
+  if ((rc = prof_events(h, 0, &e0, &e1)) || (rc = deals_enter_launch(h, s, L, cycle_kernel, P, &tag))) return rc;
+  if (cycle_kernel) {
     const int S = h->cycle_s;
-    hipExtLaunchKernelGGL(find_kernel(kCycleKernels, kernel_key(h->P.L.N, ind, h->rec_planar)), dim3((h->P.tiles + S - 1) / S), dim3(2 * S * SK_TILE), (uint32_t)h->lds_cycle, s,
-                          e0, e1, 0, h->P, rec, act_out, iters, policy_seed, h->iter, tag, (uint32_t)h->lds_cycle_step, h->cycle_deal_arg, cycle_len);
+    hipExtLaunchKernelGGL(find_kernel(kCycleKernels, kernel_key(P.L.N, ind, h->rec_planar)), dim3((P.tiles + S - 1) / S), dim3(2 * S * SK_TILE), (uint32_t)h->lds_cycle, s,
+                          e0, e1, 0, P, rec, act_out, L.iters, policy_seed, h->iter, tag, (uint32_t)h->lds_cycle_step, h->cycle_deal_arg, L.cycles > 1 ? L.iters / L.cycles : 0);
   } else {
-    if ((rc = flush_planned(h, s))) return rc;  // (another kind of step: a planned run does not wait for a k_cycle launch)
-    hipExtLaunchKernelGGL(find_kernel(kStepKernels, kernel_key(fixed_players(h->P.L.N), ind, ind && !policy && planar_out, policy)), dim3(h->P.tiles), dim3(SK_TILE), (uint32_t)(policy ? h->lds_rollout : h->lds_step), s, e0, e1, 0, h->P, actions, rec, act_out,
-                          iters, policy_seed, h->iter, end_rew, end_flag, raw_out, h->raw_stride);
+    hipExtLaunchKernelGGL(find_kernel(kStepKernels, kernel_key(fixed_players(P.L.N), ind, ind && !policy && planar_out, policy)), dim3(P.tiles), dim3(SK_TILE), (uint32_t)(policy ? h->lds_rollout : h->lds_step), s, e0, e1, 0, P, actions, rec, act_out,
+                          L.iters, policy_seed, h->iter, end_rew, end_flag, raw_out, h->raw_stride);
   }
   HIPCHK(hipGetLastError());
-  h->P.ov_flags = 0;
-  h->iters_total += (uint64_t)iters;
-  if (policy) h->iter += (uint64_t)iters;  // the policy's Philox counter counts rollout iterations only
-  h->pending_iters += iters;
+  h->iters_total += (uint64_t)L.iters;
+  if (policy) h->iter += (uint64_t)L.iters;  // the policy's Philox counter counts rollout iterations only
   return SKYJO_OK;
 }
 
@@ -536,15 +565,14 @@ void resolve_form(skyjo_vec *h) {
   h->form = one      ? DealForm::OneKernel
             : beside ? (h->req.unpipelined ? DealForm::TwoStreamsScanPublish : DealForm::TwoStreamsPipelined)
                      : (h->req.inline_work_list ? DealForm::InlineWorkList : DealForm::InlineScan);
-  h->interval_default = deal_interval_default(N, h->form, h->cycle_s);
-  if (h->auto_interval) h->deal_every_iters = h->interval_default;
+  deals_set_interval_default(h, deal_interval_default(N, h->form, h->cycle_s));
 }
 
 // Every option that changes a request goes through here: nothing runs and nothing is in flight in the old form when the new one
 // takes over (the caller's stream may be a non-blocking one, so the device is synchronised before the null stream publishes).
 int change_form(skyjo_vec *h, const DealRequests &req) {
   HIPCHK(hipDeviceSynchronize());
-  int rc = publish_deals(h, nullptr);
+  int rc = deals_drain(h, nullptr);
   if (rc) return rc;
   HIPCHK(hipDeviceSynchronize());
   h->req = req;
@@ -708,7 +736,7 @@ int skyjo_vec_create(const skyjo_vec_config *cfg, skyjo_vec **out) {
   resolve_form(h);
   if (const char *e = sk_diag_env("SKYJO_DEAL_INTERVAL")) {
     const int v = atoi(e);
-    if (v >= 1 && v <= 1024) h->deal_every_iters = v, h->auto_interval = false;
+    if (v >= 1 && v <= 1024) deals_set_interval(h, v);
   }
   *out = h;
   return SKYJO_OK;
@@ -753,19 +781,17 @@ int skyjo_vec_seed(skyjo_vec *h, const uint64_t *seeds_host, uint64_t base_seed,
   HIPCHK(hipMemsetAsync(h->P.done, 0, h->G, s));
   HIPCHK(hipMemsetAsync(h->P.dev_error, 0, sizeof(uint32_t), s));  // a new seeding starts from a clean slate
   h->health_host[2] = 0;
-  int rc0;
-  if ((rc0 = publish_deals(h, s))) return rc0;  // drain the dealing pipeline of the previous seeding, if any
+  int rc;
+  if ((rc = deals_drain(h, s))) return rc;  // drain the dealing pipeline of the previous seeding, if any
   hipLaunchKernelGGL(k_seed, dim3((h->P.B + 255) / 256), dim3(256), 0, s, h->P, (const uint64_t *)d_seeds, base_seed, 0,
                      h->P.B);
   HIPCHK(hipGetLastError());
-  int rc;
   // set_seed deals immediately (skyjo.py:88): deal #0 becomes the live game, the following ones fill the bank
-  h->inflight = InFlight::None;
-  if ((rc = start_deals(h, s)) || (rc = publish_deals(h, s))) return rc;
+  if ((rc = deals_refill(h, s))) return rc;
   h->seeded = true;
   if ((rc = skyjo_vec_reset(h, nullptr, nullptr, stream))) return rc;
   for (int k = 1; k < SK_BANK; k++)
-    if ((rc = start_deals(h, s)) || (rc = publish_deals(h, s))) return rc;
+    if ((rc = deals_refill(h, s))) return rc;
   if (d_seeds) {
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipFree(d_seeds));
@@ -783,20 +809,20 @@ int skyjo_vec_seed_one(skyjo_vec *h, int32_t game, uint64_t value, void *stream)
   h->raw_valid = false;
   hipStream_t s = (hipStream_t)stream;
   int rc;
-  if ((rc = ensure_scratch(h)) || (rc = publish_deals(h, s))) return rc;  // nobody else may be using the stream that is re-seeded
+  if ((rc = ensure_scratch(h)) || (rc = deals_drain(h, s))) return rc;  // nobody else may be using the stream that is re-seeded
   uint64_t *d_seed = (uint64_t *)h->d_actions;                               // (8 bytes of the host-style scratch)
   HIPCHK(hipMemcpyAsync(d_seed, &value, sizeof(value), hipMemcpyHostToDevice, s));
   HIPCHK(hipStreamSynchronize(s));  // (`value` lives on this stack frame)
   hipLaunchKernelGGL(k_seed, dim3(1), dim3(64), 0, s, h->P, (const uint64_t *)d_seed, (uint64_t)0, (int)game, 1);
   HIPCHK(hipGetLastError());
-  if ((rc = start_deals(h, s)) || (rc = publish_deals(h, s))) return rc;  // deal #0 of the new stream ...
+  if ((rc = deals_refill(h, s))) return rc;  // deal #0 of the new stream ...
   HIPCHK(hipMemsetAsync(h->d_mask, 0, h->G, s));
   const uint8_t one = 1;
   HIPCHK(hipMemcpyAsync(h->d_mask + game, &one, 1, hipMemcpyHostToDevice, s));
   HIPCHK(hipStreamSynchronize(s));
   if ((rc = skyjo_vec_reset(h, h->d_mask, nullptr, stream))) return rc;    // ... becomes the live game
   for (int k = 1; k < SK_BANK; k++)
-    if ((rc = start_deals(h, s)) || (rc = publish_deals(h, s))) return rc;
+    if ((rc = deals_refill(h, s))) return rc;
   return SKYJO_OK;
 }
 
@@ -806,7 +832,7 @@ int skyjo_vec_snapshot_create(skyjo_vec *h, skyjo_vec_snapshot **out, void *stre
   GUARD(h);
   hipStream_t s = (hipStream_t)stream;
   int rc;
-  if ((rc = publish_deals(h, s))) return rc;  // no deal in flight: the arrays below are the whole truth
+  if ((rc = deals_drain(h, s))) return rc;  // no deal in flight: the arrays below are the whole truth
   HIPCHK(hipDeviceSynchronize());
   if ((rc = dev_error_fetch(h, s))) return rc;   // (a voided run is not worth keeping)
   skyjo_vec_snapshot *sn = new (std::nothrow) skyjo_vec_snapshot();
@@ -832,9 +858,8 @@ int skyjo_vec_snapshot_create(skyjo_vec *h, skyjo_vec_snapshot **out, void *stre
     delete sn;
     return fail(SKYJO_E_DEVICE, std::string("snapshot copy: ") + hipGetErrorString(e));
   }
-  sn->pending_iters = h->pending_iters, sn->deal_every_iters = h->deal_every_iters, sn->calm_runs = h->calm_runs;
-  sn->list_sel = h->list_sel, sn->auto_interval = h->auto_interval, sn->health_seen = h->health_seen;
-  sn->deal_tag = h->deal_tag, sn->iter = h->iter, sn->iters_total = h->iters_total;
+  sn->deal = h->deal.st;  // (nothing in flight: the state is the whole schedule)
+  sn->iter = h->iter, sn->iters_total = h->iters_total;
   sn->health[0] = h->health_host[0], sn->health[1] = h->health_host[1];
   *out = sn;
   return SKYJO_OK;
@@ -852,7 +877,7 @@ int skyjo_vec_snapshot_restore(skyjo_vec *h, const skyjo_vec_snapshot *sn, void 
   GUARD(h);
   hipStream_t s = (hipStream_t)stream;
   int rc;
-  if ((rc = publish_deals(h, s))) return rc;
+  if ((rc = deals_drain(h, s))) return rc;
   HIPCHK(hipDeviceSynchronize());
   size_t off = 0;
   for (size_t k = 0; k < sn->array_bytes.size(); k++) {  // (arrays allocated after the snapshot are not part of it)
@@ -861,12 +886,10 @@ int skyjo_vec_snapshot_restore(skyjo_vec *h, const skyjo_vec_snapshot *sn, void 
     off += (a.second + 255) & ~(size_t)255;
   }
   HIPCHK(hipStreamSynchronize(s));
-  h->pending_iters = sn->pending_iters, h->deal_every_iters = sn->deal_every_iters, h->calm_runs = sn->calm_runs;
-  h->list_sel = sn->list_sel, h->auto_interval = sn->auto_interval, h->health_seen = sn->health_seen;
-  h->deal_tag = sn->deal_tag, h->P.deal_tag = sn->deal_tag, h->iter = sn->iter, h->iters_total = sn->iters_total;
+  h->deal.st = sn->deal, h->P.deal_tag = sn->deal.deal_tag;  // (the drain above left nothing in flight; form and options stay today's)
+  h->iter = sn->iter, h->iters_total = sn->iters_total;
   h->health_host[0] = sn->health[0], h->health_host[1] = sn->health[1];
   h->health_host[2] = 0;  // the restored device word is clean (snapshot_create refuses a voided run): so is the host's copy
-  h->inflight = InFlight::None;
   h->raw_valid = false;
   return SKYJO_OK;
 }
@@ -888,15 +911,14 @@ int skyjo_vec_snapshot_destroy(skyjo_vec_snapshot *sn) {
 static int reset_impl(skyjo_vec *h, const uint8_t *mask, void *records_out, hipStream_t s, uint8_t *raw_out, int planar = 0) {
   int rc;
   h->raw_valid = false;
-  if ((rc = publish_deals(h, s))) return rc;  // make every dealt episode available
+  if ((rc = deals_drain(h, s))) return rc;  // make every dealt episode available
   dim3 grid(h->P.tiles), block(SK_TILE);
   if (h->P.L.indirect)
     hipLaunchKernelGGL((k_reset<true>), grid, block, h->lds_bytes, s, h->P, mask, (uint8_t *)records_out, raw_out, h->raw_stride, planar);
   else
     hipLaunchKernelGGL((k_reset<false>), grid, block, h->lds_bytes, s, h->P, mask, (uint8_t *)records_out, raw_out, h->raw_stride, 0);
   HIPCHK(hipGetLastError());
-  if ((rc = start_deals(h, s))) return rc;  // refill what was taken (one episode per game and cycle)
-  return publish_deals(h, s);
+  return deals_refill(h, s);  // what was taken (one episode per game and cycle)
 }
 
 int skyjo_vec_reset(skyjo_vec *h, const uint8_t *mask, void *records_out, void *stream) {
@@ -907,12 +929,10 @@ int skyjo_vec_reset(skyjo_vec *h, const uint8_t *mask, void *records_out, void *
 }
 
 static int step_once(skyjo_vec *h, const int32_t *actions, void *records_out, double *end_rew, uint8_t *end_flag, hipStream_t s,
-                     uint8_t *raw_out = nullptr, bool planar_out = false) {
-  const bool due = h->pending_iters + 1 >= h->deal_every_iters;
-  if (due && plans_ahead(h)) plan_cycle(h);
-  int rc = launch_step(h, s, false, actions, (uint8_t *)records_out, nullptr, 1, 0, end_rew, end_flag, raw_out, 0, planar_out && records_out);
-  if (rc) return rc;
-  return due ? start_due_deals(h, s) : SKYJO_OK;
+                     uint8_t *raw_out = nullptr, bool planar_out = false, uint32_t host_seq = 0) {
+  const StepLaunch L = deals_plan_launch(h, 1, false);
+  const int rc = launch_step(h, s, L, false, actions, (uint8_t *)records_out, nullptr, 0, end_rew, end_flag, raw_out, planar_out && records_out, host_seq);
+  return rc ? rc : deals_finish_launch(h, s, L);
 }
 
 int skyjo_vec_step(skyjo_vec *h, const int32_t *actions, void *records_out, void *stream) {
@@ -993,34 +1013,12 @@ int skyjo_vec_rollout(skyjo_vec *h, int32_t iters, uint64_t policy_seed, void *r
   if (planar && rec && h->form != DealForm::OneKernel)
     return fail(SKYJO_E_STATE, "SKYJO_OPT_RECORD_LAYOUT = tile-planar needs the one-kernel dealing form (SKYJO_OPT_OVERLAP 3)");
   for (int done = 0; done < iters;) {
-    int n = iters - done < kMaxRolloutChunk ? iters - done : kMaxRolloutChunk;
-    // a launch ends where the next dealing run is due, so the cadence does not depend on how the caller slices its calls
-    const int due = h->deal_every_iters - h->pending_iters;
-    if (n > due) n = due > 0 ? due : 1;
-    const bool run_due = h->pending_iters + n >= h->deal_every_iters, planned = plans_ahead(h);
-    // The one-kernel form keeps its tiles in LDS over several dealing cycles when the caller asks for that many iterations at once:
-    // up to kMaxCyclesPerLaunch whole cycles in ONE launch (the cycle ends inside it are handled by the kernel: step_body, k_cycle)
-    int cycles = 1;
-    // (only where the kernel's cycle ends have a run to hand over: an engine that never deals ahead - SKYJO_OPT_NO_BANK - plans nothing,
-    // and a cycle end inside its launch would publish and plan with a stale id: ADVICE r4)
-    if (h->form == DealForm::OneKernel && planned && run_due && h->pending_iters == 0) {
-      const int cap = h->max_cycles > 0 ? h->max_cycles : kMaxCyclesPerLaunch;
-      cycles = (iters - done) / h->deal_every_iters;
-      cycles = cycles < 1 ? 1 : (cycles > cap ? cap : cycles);
-      n = cycles * h->deal_every_iters;
-    }
-    if (run_due && planned) {
-      plan_cycle(h);
-      const uint32_t first = h->deal_tag;  // the id of the first run planned by this launch; the kernel counts on from it
-      for (int c = 1; c < cycles; c++) next_deal_tag(h, false);
-      h->P.plan_new_tag = first;
-    }
-    int rc = launch_step(h, s, true, nullptr, rec, actions_out, n, policy_seed, nullptr, nullptr, nullptr, cycles > 1 ? h->deal_every_iters : 0);
-    if (rc) return rc;
-    done += n;
-    if (run_due && (rc = start_due_deals(h, s))) return rc;
-    if (rec) rec += (size_t)n * (planar ? h->G : (size_t)h->P.B) * h->P.L.rec_bytes;
-    if (actions_out) actions_out += (size_t)n * h->P.B;
+    const StepLaunch L = deals_plan_launch(h, iters - done, true);
+    int rc;
+    if ((rc = launch_step(h, s, L, true, nullptr, rec, actions_out, policy_seed)) || (rc = deals_finish_launch(h, s, L))) return rc;
+    done += L.iters;
+    if (rec) rec += (size_t)L.iters * (planar ? h->G : (size_t)h->P.B) * h->P.L.rec_bytes;
+    if (actions_out) actions_out += (size_t)L.iters * h->P.B;
   }
   return SKYJO_OK;
 }
@@ -1271,11 +1269,10 @@ int skyjo_vec_seed_raw(skyjo_vec *h, int32_t game, uint32_t value, void *stream)
   h->raw_valid = false;
   hipStream_t s = (hipStream_t)stream;
   int rc;
-  if ((rc = publish_deals(h, s))) return rc;  // nobody else may be using the stream that is re-seeded
+  if ((rc = deals_drain(h, s))) return rc;  // nobody else may be using the stream that is re-seeded
   hipLaunchKernelGGL(k_seed_raw, dim3(1), dim3(64), 0, s, h->P, game, value);
   HIPCHK(hipGetLastError());
-  if ((rc = start_deals(h, s))) return rc;
-  return publish_deals(h, s);
+  return deals_refill(h, s);
 }
 
 int skyjo_vec_rng_set_state(skyjo_vec *h, int32_t game, const uint32_t *key_host, int32_t pos, void *stream) {
@@ -1367,7 +1364,7 @@ int skyjo_vec_debug_trace(skyjo_vec *h, uint64_t *out_host) {  // [4][tiles][8]:
 int skyjo_vec_get_option(const skyjo_vec *h, int option, int64_t *value_out) {
   if (!h || !value_out) return fail(SKYJO_E_INVALID, "null argument");
   switch (option) {
-    case SKYJO_OPT_DEAL_INTERVAL: *value_out = h->deal_every_iters; return SKYJO_OK;
+    case SKYJO_OPT_DEAL_INTERVAL: *value_out = deals_interval(h); return SKYJO_OK;
     case SKYJO_OPT_OVERLAP: *value_out = h->form == DealForm::OneKernel ? 3 : uses_deal_stream(h->form) ? 2 : 0; return SKYJO_OK;
     case SKYJO_OPT_NO_BANK: *value_out = h->req.no_bank ? 1 : 0; return SKYJO_OK;
     case SKYJO_OPT_RECORD_LAYOUT: *value_out = h->rec_planar_all ? SKYJO_REC_TILE_PLANAR_ALL : h->rec_planar ? SKYJO_REC_TILE_PLANAR : SKYJO_REC_ROW_MAJOR; return SKYJO_OK;
@@ -1386,7 +1383,7 @@ int skyjo_vec_set_option(skyjo_vec *h, int option, int64_t value) {
   switch (option) {
     case SKYJO_OPT_DEAL_INTERVAL:
       if (value < 1 || value > 1024) return fail(SKYJO_E_INVALID, "deal interval must be in 1..1024");
-      h->deal_every_iters = (int)value, h->auto_interval = false;
+      deals_set_interval(h, (int)value);
       return SKYJO_OK;
     case SKYJO_OPT_OVERLAP:
       // 0: in line; 1: beside the step kernel, in the form this engine prefers; 2: the two-stream form; 3: the one-kernel form (k_cycle)
@@ -1446,61 +1443,73 @@ static int ensure_scratch(skyjo_vec *h) {
   return SKYJO_OK;
 }
 
+// The buffers a *_host call works through, chosen once per call: where the host puts the actions (or players) and the mask and gets
+// the records, and what the kernels are given for them.  Mapped: both are the host-mapped block, a put / get is a memcpy and the
+// kernel also exports whole games where the engine does that (raw_d).  Staged: both are the device scratch, made when the first
+// such call needs it, and a put / get is a hipMemcpy on the null stream.
+struct HostBufs {
+  bool mapped;
+  int32_t *actions, *actions_d;
+  uint8_t *mask, *mask_d, *records, *records_d;
+  uint8_t *raw_d;  // the raw export's target, or null
+};
+static int host_bufs(skyjo_vec *h, HostBufs *b) {
+  if (h->fast_host) {
+    *b = {true, h->hm_actions, h->hm_actions_d, h->hm_mask, h->hm_mask_d, h->hm_records, h->hm_records_d, h->raw_export ? h->hm_raw_d : nullptr};
+    return SKYJO_OK;
+  }
+  if (int rc = ensure_scratch(h)) return rc;
+  *b = {false, h->d_actions, h->d_actions, h->d_mask, h->d_mask, h->d_records, h->d_records, nullptr};
+  return SKYJO_OK;
+}
+static int host_copy(const HostBufs &b, void *dst, const void *src, size_t bytes, hipMemcpyKind staged_kind) {  // a put or a get
+  if (b.mapped) memcpy(dst, src, bytes);
+  else HIPCHK(hipMemcpy(dst, src, bytes, staged_kind));
+  return SKYJO_OK;
+}
+static int host_put(const HostBufs &b, void *dst, const void *src_host, size_t bytes) { return host_copy(b, dst, src_host, bytes, hipMemcpyHostToDevice); }
+static int host_get(const HostBufs &b, void *dst_host, const void *src, size_t bytes) { return host_copy(b, dst_host, src, bytes, hipMemcpyDeviceToHost); }
+// The launches are through before the host reads on: the null stream is synchronised unless the kernel's sign-off word `arrived`
+// or a staged get follows, which synchronises itself.
+static int host_wait(const HostBufs &b, bool arrived, bool get_follows) {
+  if (!arrived && (b.mapped || !get_follows)) HIPCHK(hipStreamSynchronize(nullptr));
+  return SKYJO_OK;
+}
+
+// (host-style records are row-major whatever the layout option)
 int skyjo_vec_step_host(skyjo_vec *h, const int32_t *actions_host, void *records_out_host) {
   if (!h || !actions_host) return fail(SKYJO_E_INVALID, "null argument");
   GUARD(h);
   if (!h->seeded) return fail(SKYJO_E_STATE, "skyjo_vec_seed must be called first");
-  if (h->fast_host) {  // actions read from / records and whole games written to host-mapped memory: one launch, one synchronisation
-    memcpy(h->hm_actions, actions_host, sizeof(int32_t) * (size_t)h->P.B);
-    // A single tile is a single wavefront: it signs off with a sequence number in host-mapped memory as its very last
-    // store, and the host spins on that word - a stream synchronisation costs ~10 us more than the kernel takes.  (The
-    // stream stays ordered: whatever is launched next runs behind this kernel as usual.)
-    const bool spin = h->P.tiles == 1 && h->host_spin;
-    if (spin) {
-      h->host_seq = h->host_seq + 1 ? h->host_seq + 1 : 1;
-      h->P.host_seq = h->host_seq;
-    }
-    int rc = step_once(h, h->hm_actions_d, h->hm_records_d, nullptr, nullptr, nullptr, h->raw_export ? h->hm_raw_d : nullptr);
-    h->P.host_seq = 0;
-    if (rc) return rc;
-    bool arrived = false;
-    if (spin) {
-      const volatile uint32_t *flag = h->health_host + 3;
-      for (long k = 0; k < 4000000 && !(arrived = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == h->host_seq); k++) __builtin_ia32_pause();
-    }
-    if (!arrived) HIPCHK(hipStreamSynchronize(nullptr));  // (also the fallback when the word does not come: ~0.1 s of spinning)
-    h->raw_valid = h->raw_export;
-    if (records_out_host) memcpy(records_out_host, h->hm_records, (size_t)h->P.B * h->P.L.rec_bytes);
-    return dev_error_check(h);
+  HostBufs b;
+  int rc;
+  if ((rc = host_bufs(h, &b)) || (rc = host_put(b, b.actions, actions_host, sizeof(int32_t) * (size_t)h->P.B))) return rc;
+  // Mapped: actions read from / records and whole games written to host-mapped memory - one launch, one synchronisation.
+  // A single tile is a single wavefront: it signs off with a sequence number in host-mapped memory as its very last
+  // store, and the host spins on that word - a stream synchronisation costs ~10 us more than the kernel takes.  (The
+  // stream stays ordered: whatever is launched next runs behind this kernel as usual.)
+  const bool spin = b.mapped && h->P.tiles == 1 && h->host_spin;
+  if (spin) h->host_seq = h->host_seq + 1 ? h->host_seq + 1 : 1;
+  if ((rc = step_once(h, b.actions_d, b.records_d, nullptr, nullptr, nullptr, b.raw_d, false, spin ? h->host_seq : 0))) return rc;
+  bool arrived = false;
+  if (spin) {
+    const volatile uint32_t *flag = h->health_host + 3;
+    for (long k = 0; k < 4000000 && !(arrived = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == h->host_seq); k++) __builtin_ia32_pause();
   }
-  int rc = ensure_scratch(h);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(h->d_actions, actions_host, sizeof(int32_t) * (size_t)h->P.B, hipMemcpyHostToDevice));
-  if ((rc = skyjo_vec_step(h, h->d_actions, h->d_records, nullptr))) return rc;
-  if (records_out_host)
-    HIPCHK(hipMemcpy(records_out_host, h->d_records, (size_t)h->P.B * h->P.L.rec_bytes, hipMemcpyDeviceToHost));
-  else
-    HIPCHK(hipStreamSynchronize(nullptr));
+  if ((rc = host_wait(b, arrived, records_out_host != nullptr))) return rc;  // (also the fallback when the word does not come: ~0.1 s of spinning)
+  h->raw_valid = b.raw_d != nullptr;
+  if (records_out_host && (rc = host_get(b, records_out_host, b.records, (size_t)h->P.B * h->P.L.rec_bytes))) return rc;
   return dev_error_check(h);
 }
 
 int skyjo_vec_observe_host(skyjo_vec *h, const int32_t *players_host, void *records_out_host) {
   if (!h || !records_out_host) return fail(SKYJO_E_INVALID, "null argument");
   GUARD(h);
-  if (h->fast_host) {  // (the games do not change: a valid host copy of them stays valid)
-    if (players_host) memcpy(h->hm_actions, players_host, sizeof(int32_t) * (size_t)h->P.B);
-    int rc = observe_impl(h, players_host ? h->hm_actions_d : nullptr, h->hm_records_d, nullptr, 0);  // (host-style records are row-major whatever the option)
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    memcpy(records_out_host, h->hm_records, (size_t)h->P.B * h->P.L.rec_bytes);
-    return dev_error_check(h);
-  }
-  int rc = ensure_scratch(h);
-  if (rc) return rc;
-  if (players_host)
-    HIPCHK(hipMemcpy(h->d_actions, players_host, sizeof(int32_t) * (size_t)h->P.B, hipMemcpyHostToDevice));
-  if ((rc = observe_impl(h, players_host ? h->d_actions : nullptr, h->d_records, nullptr, 0))) return rc;
-  HIPCHK(hipMemcpy(records_out_host, h->d_records, (size_t)h->P.B * h->P.L.rec_bytes, hipMemcpyDeviceToHost));
+  HostBufs b;  // (the games do not change: a valid host copy of them stays valid)
+  int rc;
+  if ((rc = host_bufs(h, &b)) || (players_host && (rc = host_put(b, b.actions, players_host, sizeof(int32_t) * (size_t)h->P.B)))) return rc;
+  if ((rc = observe_impl(h, players_host ? b.actions_d : nullptr, b.records_d, nullptr, 0)) || (rc = host_wait(b, false, true))) return rc;
+  if ((rc = host_get(b, records_out_host, b.records, (size_t)h->P.B * h->P.L.rec_bytes))) return rc;
   return dev_error_check(h);
 }
 
@@ -1508,23 +1517,12 @@ int skyjo_vec_reset_host(skyjo_vec *h, const uint8_t *mask_host, void *records_o
   if (!h) return fail(SKYJO_E_INVALID, "null handle");
   GUARD(h);
   if (!h->seeded) return fail(SKYJO_E_STATE, "skyjo_vec_seed must be called first");
-  if (h->fast_host) {
-    if (mask_host) memcpy(h->hm_mask, mask_host, (size_t)h->P.B);
-    int rc = reset_impl(h, mask_host ? h->hm_mask_d : nullptr, h->hm_records_d, nullptr, h->raw_export ? h->hm_raw_d : nullptr);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    h->raw_valid = h->raw_export;
-    if (records_out_host) memcpy(records_out_host, h->hm_records, (size_t)h->P.B * h->P.L.rec_bytes);
-    return dev_error_check(h);
-  }
-  int rc = ensure_scratch(h);
-  if (rc) return rc;
-  if (mask_host) HIPCHK(hipMemcpy(h->d_mask, mask_host, (size_t)h->P.B, hipMemcpyHostToDevice));
-  if ((rc = skyjo_vec_reset(h, mask_host ? h->d_mask : nullptr, h->d_records, nullptr))) return rc;
-  if (records_out_host)
-    HIPCHK(hipMemcpy(records_out_host, h->d_records, (size_t)h->P.B * h->P.L.rec_bytes, hipMemcpyDeviceToHost));
-  else
-    HIPCHK(hipStreamSynchronize(nullptr));
+  HostBufs b;
+  int rc;
+  if ((rc = host_bufs(h, &b)) || (mask_host && (rc = host_put(b, b.mask, mask_host, (size_t)h->P.B)))) return rc;
+  if ((rc = reset_impl(h, mask_host ? b.mask_d : nullptr, b.records_d, nullptr, b.raw_d)) || (rc = host_wait(b, false, records_out_host != nullptr))) return rc;
+  h->raw_valid = b.raw_d != nullptr;
+  if (records_out_host && (rc = host_get(b, records_out_host, b.records, (size_t)h->P.B * h->P.L.rec_bytes))) return rc;
   return dev_error_check(h);
 }
 

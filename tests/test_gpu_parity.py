@@ -166,6 +166,54 @@ def test_step_vs_oracle_random_actions(N, ind, rng_mode, B):
     eng.close()
 
 
+def test_host_calls_staged_through_device_scratch_vs_oracle():
+    """The *_host calls of an engine of more than 4 096 game slots are staged through device scratch instead of the host-mapped
+    block.  4 097 games are 65 tiles, 4 160 slots: the smallest engine on that path (4 096, the largest on the mapped one, is a
+    case of test_step_vs_oracle_random_actions).  40 iterations of observe_host / step_host / rewards_host with that test's
+    actions, a reset_host of 5 % of the games and one more observe_host, each held to the oracle."""
+    B, N = 4097, 2
+    cfg = dict(num_players=N, score_penalty=2.0, observe_other_player_indirect=True, mean_reward=1.0,
+               reward_refunded=0.001, rng_mode=0, auto_reset=True)
+    eng = _engine(B, **cfg)
+    ora = _oracle_vec(num_envs=B, **cfg)
+    eng.seed(None, 1234)
+    ora.seed(None, 1234)
+    rng = np.random.default_rng(7)
+
+    def same_view(o, tag):
+        obs, mask, agent, phase = ora.observe()
+        np.testing.assert_array_equal(o.observations, obs, err_msg=f"obs {tag}")
+        np.testing.assert_array_equal(o.action_mask, mask, err_msg=f"mask {tag}")
+        np.testing.assert_array_equal(o.agent, agent, err_msg=f"agent {tag}")
+        np.testing.assert_array_equal(o.phase, phase, err_msg=f"phase {tag}")
+        return mask
+
+    for t in range(40):
+        mask = same_view(eng.observe_host(), f"t={t}")
+        # uniformly random legal action, 0.2 % illegal ones
+        acts = np.argmax(rng.random((B, 26)) * mask, axis=1).astype(np.int32)
+        bad = rng.random(B) < 0.002
+        acts[bad] = rng.integers(-2, 29, size=int(bad.sum()))
+        ora.step(acts)
+        o = eng.step_host(acts)
+        np.testing.assert_array_equal(o.status, ora.status, err_msg=f"status t={t}")
+        np.testing.assert_array_equal(o.done, ora.dones, err_msg=f"done t={t}")
+        rew, sc, done = eng.rewards_host()
+        dn = ora.dones.astype(bool)
+        np.testing.assert_array_equal(rew[dn], ora.rewards[dn], err_msg=f"rewards t={t}")
+    m = (rng.random(B) < 0.05).astype(np.uint8)
+    ora.reset(m)
+    o = eng.reset_host(m)
+    same_view(o, "after reset_host")
+    np.testing.assert_array_equal(o.done, ora.dones, err_msg="done after reset_host")
+    same_view(eng.observe_host(), "after reset_host, observed")
+    c, oc = eng.counters(), ora.counters()
+    for k in ("steps", "episodes", "illegal", "resets", "sum_len"):
+        assert c[k] == oc[k], (k, c[k], oc[k])
+    assert c["illegal"] > 0
+    eng.close()
+
+
 @pytest.mark.parametrize("N,ind,rng_mode,B", [(3, True, 0, 4096), (2, True, 0, 4096), (4, True, 1, 2048),
                                               (3, False, 1, 777), (12, True, 0, 128),
                                               # k_cycle with two / three step wavefronts per workgroup and a last workgroup that is not full

@@ -157,6 +157,63 @@ def test_snapshot_restore_round_trip():
     eng.close()
 
 
+_SNAP_B, _SNAP_SEED, _SNAP_POLICY = 192, 11, 4  # three tiles, as the cadence test of tests/test_gpu_parity.py
+_snap_reference = {}
+
+
+def _snapshot_window(eng):
+    """48 iterations with records and actions, then the counters."""
+    import torch
+
+    rec = eng.new_records(48)
+    act = torch.empty((48, _SNAP_B), dtype=torch.int32, device="cuda")
+    eng.rollout(48, policy_seed=_SNAP_POLICY, records=rec, actions=act)
+    return rec, act, eng.counters()
+
+
+def _snapshot_reference():
+    """The same 13 + 48 iterations on an engine in its default form, without a snapshot (made once, shared by the five forms)."""
+    if not _snap_reference:
+        eng = _engine(_SNAP_B, **CFG)
+        eng.seed(None, _SNAP_SEED)
+        eng.rollout(13, policy_seed=_SNAP_POLICY)
+        rec, act, _ = _snapshot_window(eng)
+        _snap_reference.update(rec=rec.cpu(), act=act.cpu())
+        eng.close()
+    return _snap_reference["rec"], _snap_reference["act"]
+
+
+@pytest.mark.parametrize("overlap,option,form", [(0, None, "in line"), (0, "OPT_INLINE_WORK_LIST", "in line"), (2, None, "two streams"),
+                                                 (2, "OPT_UNPIPELINED", "two streams"), (3, None, "one kernel")],
+                         ids=["in_line", "in_line_work_list", "two_streams", "two_streams_unpipelined", "one_kernel"])
+def test_snapshot_restore_in_every_dealing_form(overlap, option, form):
+    """A snapshot holds the dealing schedule's host state as one value: taken in every dealing form with a run in flight and the
+    cycle under way (interval 8, 13 iterations: pending = 5), run on, restored and run again, the engine writes bit-equal records
+    and actions both times - and the ones an engine in its default form writes without any snapshot."""
+    import torch
+    from skyjo_rl_amd import _lib
+
+    eng = _engine(_SNAP_B, **CFG)
+    eng.set_deal_interval(8)
+    eng.set_overlap(overlap)
+    if option:
+        eng.set_option(getattr(_lib, option), 1)
+    assert eng.dealing_form() == form
+    eng.seed(None, _SNAP_SEED)
+    eng.rollout(13, policy_seed=_SNAP_POLICY)
+    snap = eng.snapshot()
+    x_rec, x_act, cx = _snapshot_window(eng)
+    eng.restore(snap)
+    y_rec, y_act, cy = _snapshot_window(eng)
+    z_rec, z_act = _snapshot_reference()
+    assert torch.equal(x_rec, y_rec) and torch.equal(x_act, y_act)
+    assert torch.equal(x_rec.cpu(), z_rec) and torch.equal(x_act.cpu(), z_act)
+    for k in ("steps", "episodes", "resets", "sum_len", "waits"):
+        assert cx[k] == cy[k], k
+    snap.close()
+    eng.close()
+
+
 def test_handle_runs_on_its_device_from_any_thread():
     """every entry point switches to the handle's device and restores the caller's.  On this one-GPU box the
     observable part is: calls from a fresh thread (whose current device was never set) work and leave torch's current
