@@ -333,8 +333,11 @@ int skyjo_vec_sample_actions(skyjo_vec *h, const void *records, const float *log
 
 /* The policy net of config 5 on the matrix cores: RLlib's default fully connected net as the reference's
  * TorchActionMaskModel builds it (rlskyjo/models/action_mask_model.py:41-52: obs -> 256 tanh -> 256 tanh -> outputs),
- * evaluated for n records in one kernel that reads the int8 observation out of each record (indirect observation,
- * obs_dim <= 31).  Weights are given once in torch.nn.Linear layout (row-major [out][in], float32, HOST pointers) and
+ * evaluated for n records in one kernel that reads the int8 observation out of each record: 1 <= obs_dim <= 163, either
+ * observation (31 features indirect, 19 + 12 N direct: 43 at two players, 67 at four, 163 at twelve).  Up to 31 inputs run in
+ * k_net_bf16 / k_net_split, more in their wide forms (k_net_bf16_wide / k_net_split_wide: layer 1's weights read from memory, everything
+ * behind it the same code), which read the first 16 * (obs_dim / 16 + 1) bytes of every record: record_bytes must hold them, as an
+ * engine's records of that obs_dim do (SKYJO_E_INVALID otherwise, nothing launched).  Weights are given once in torch.nn.Linear layout (row-major [out][in], float32, HOST pointers) and
  * kept on the device as bf16 MFMA fragments (one per weight, or a high and a low one: see SKYJO_MLP_*); accumulation is
  * float32.  out: float32 [n][out_dim] (device), out_dim <= 32 (26 logits for the policy branch, 1 for the value branch).
  * tests/test_gpu_policy_net.py states the tolerance of either precision against the float32 torch module. */
@@ -388,13 +391,16 @@ int skyjo_vec_episode_ends_layout(skyjo_vec *h, const void *records, int32_t lay
  * The packed layout (one kernel writes it, for skyjo_vec_mlp_create - from its host arrays, staged on the device - and for the calls
  * below; fragment = 8 bf16 values = 16 bytes, value j of lane l, hh = l >> 5; S = 2 / ln 2
  * rounded to float32, bf16(x) = round to nearest even on the bit pattern, every product and difference one rounded float32 operation):
- *   w1  [8 u][2 s][64 l] fragments   bf16(S * W1[32 u + (l & 31)][k]), k = 16 s + 8 hh + j; k in [obs_dim, 31) holds 0, k = 31 holds b1
+ *   w1  [8 u][KS s][64 l] fragments  bf16(S * W1[32 u + (l & 31)][k]), k = 16 s + 8 hh + j, over KS = max(2, obs_dim / 16 + 1) k-steps (integer
+ *                                    division) = K = 16 KS columns: k in [obs_dim, K - 1) holds 0, k = K - 1 holds b1.  obs_dim <= 31: KS = 2, b1 in
+ *                                    column 31; 47: K = 48, b1 in the last free column; 48: KS = 4; 163: KS = 11
  *   w2  [8 u][16 ks][64 l]           hi(S * W2[32 u + (l & 31)][acc_k]), acc_k = 32 (ks >> 1) + 16 (ks & 1) + 8 (j >> 2) + 4 hh + (j & 3)
  *   w3  [16 ks][64 l]                hi(W3[l & 31][acc_k]); the rows >= out_dim hold hi(0)
  *   b2  float32 [256]                S * b2[u];  bf16 mode: + sum over k = 0 .. 255, ascending, in double, of bf16(S * W2[u][k])
  *   b3  float32 [64 l][16 r]         b3[row], row = (r & 3) + 8 (r >> 2) + 4 hh; bf16 mode: + the same sum of bf16(W3[row][k]); rows >= out_dim 0
  *   w1l, w2l, w3l                    SKYJO_MLP_FP32 only, the layouts of w1, w2, w3: lo(v) = bf16(v - float(bf16(v))) of the same v
- * with hi(v) = bf16(v) for SKYJO_MLP_FP32 and bf16(-2 v) for SKYJO_MLP_BF16.
+ * with hi(v) = bf16(v) for SKYJO_MLP_FP32 and bf16(-2 v) for SKYJO_MLP_BF16.  Only w1 / w1l depend on obs_dim; in a handle's blob every piece
+ * starts on a 256-byte boundary, in this order.
  *
  * skyjo_vec_mlp_update: the six arrays are device float32 arrays in torch.nn.Linear layout - [256][obs_dim], [256], [256][256], [256],
  * [out_dim][256], [out_dim] - with obs_dim, out_dim and the precision the handle was created with; w2 and w3 16-byte aligned.
@@ -469,7 +475,11 @@ int skyjo_vec_step_collect(skyjo_vec *h, const int32_t *actions, void *records_o
  *   values         float32 [T+1][num_envs][value out_dim]  (required iff `value` is given; [T] = bootstrap value)
  *   final_rewards  double [T][num_envs][num_players] and episode_end uint8 [T][num_envs]: both or neither
  * The draw of iteration t uses (seed, first_ticket + t) as in skyjo_vec_mlp_act: the same call sequence made one launch at a
- * time from the host gives the same bits. */
+ * time from the host gives the same bits.
+ * Either observation: the policy net (26 outputs) must live on the engine's device and have the engine's obs_dim, the value net the
+ * policy net's obs_dim, precision and device (SKYJO_E_INVALID otherwise).  The learner's native branches (skyjo_vec_mlp_train_*,
+ * skyjo_vec_ppo_update) keep 1 <= obs_dim <= 31: a wider model trains through the caller's autograd on the native batches and loss head,
+ * with skyjo_vec_mlp_adam_step behind it. */
 typedef struct skyjo_vec_rollout_buffers {
   void *records;
   int32_t *actions;

@@ -958,8 +958,8 @@ static int model_check(skyjo_vec *h, const skyjo_vec_mlp *policy, const skyjo_ve
     return fail(SKYJO_E_INVALID, "skyjo_vec_model_rollout: final_rewards and episode_end go together");
   if (!h->seeded) return fail(SKYJO_E_STATE, "skyjo_vec_seed must be called first");
   if (policy->net.out_dim != SKYJO_NUM_ACTIONS) return fail(SKYJO_E_INVALID, "the policy net needs 26 outputs");
-  if (policy->device_id != h->cfg.device_id || policy->obs_dim != h->P.L.D || !h->P.L.indirect)
-    return fail(SKYJO_E_INVALID, "the policy net must live on the engine's device and take the engine's (indirect) observation");
+  if (policy->device_id != h->cfg.device_id || policy->obs_dim != h->P.L.D)
+    return fail(SKYJO_E_INVALID, "the policy net must live on the engine's device and take the engine's observation (obs_dim)");
   if (value && (policy->obs_dim != value->obs_dim || policy->device_id != value->device_id || policy->net.split != value->net.split))
     return fail(SKYJO_E_INVALID, "policy and value net must share the observation size, the precision and the device");
   return SKYJO_OK;

@@ -27,8 +27,8 @@ extern "C" {
 int skyjo_vec_mlp_create(int32_t device_id, int32_t obs_dim, int32_t out_dim, int32_t precision, const float *w1, const float *b1,
                          const float *w2, const float *b2, const float *w3, const float *b3, skyjo_vec_mlp **out) {
   if (!out || !w1 || !b1 || !w2 || !b2 || !w3 || !b3) return fail(SKYJO_E_INVALID, "null argument");
-  if (obs_dim < 1 || obs_dim > SKP_IN - 1 || out_dim < 1 || out_dim > SKP_OUT)
-    return fail(SKYJO_E_INVALID, "skyjo_vec_mlp: obs_dim must be 1..31 and out_dim 1..32");
+  if (obs_dim < 1 || obs_dim > SKP_MAX_OBS || out_dim < 1 || out_dim > SKP_OUT)
+    return fail(SKYJO_E_INVALID, "skyjo_vec_mlp: obs_dim must be 1..163 and out_dim 1..32");
   if (precision != SKYJO_MLP_BF16 && precision != SKYJO_MLP_FP32) return fail(SKYJO_E_INVALID, "skyjo_vec_mlp: unknown precision");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) return fail(SKYJO_E_INVALID, "device_id out of range");
@@ -36,7 +36,7 @@ int skyjo_vec_mlp_create(int32_t device_id, int32_t obs_dim, int32_t out_dim, in
   const bool split = precision == SKYJO_MLP_FP32;
   skyjo_vec_mlp *m = new skyjo_vec_mlp();
   m->device_id = device_id, m->obs_dim = obs_dim, m->out_dim = m->net.out_dim = out_dim;
-  if (hipMalloc(&m->blob, skp_piece_offset(8, split)) != hipSuccess) {
+  if (hipMalloc(&m->blob, skp_piece_offset(8, split, skp_w1_ksteps(obs_dim))) != hipSuccess) {
     delete m;
     return fail(SKYJO_E_DEVICE, "hipMalloc failed for the packed weights");
   }
@@ -44,7 +44,7 @@ int skyjo_vec_mlp_create(int32_t device_id, int32_t obs_dim, int32_t out_dim, in
   // tensor in front of w2 and of w3 is a multiple of SKP_HIDDEN floats, so the two are 16-byte aligned as sku_elem4 needs them.
   static_assert(SKP_HIDDEN % 4 == 0, "w2 and w3 are staged at multiples of SKP_HIDDEN floats: sku_elem4 reads them 16 bytes at a time");
   SkUpdArgs a{};
-  skp_blob_views(m->blob, split, m->net, a);
+  skp_blob_views(m->blob, split, obs_dim, m->net, a);
   a.obs_dim = obs_dim, a.out_dim = out_dim;
   const float *const src[SKU_TENSORS] = {w1, b1, w2, b2, w3, b3};
   DevBuf stage;
@@ -82,7 +82,7 @@ namespace {
 // k_mlp_update's view of the blob and the net's dimensions, with a call's tensors
 bool mlp_update_args(const skyjo_vec_mlp *m, const float *const p[SKU_TENSORS], SkUpdArgs &a) {
   SkMlpDev net{};  // (the net kernels' view of the same blob: m->net holds it already)
-  skp_blob_views(m->blob, m->net.split != 0, net, a);
+  skp_blob_views(m->blob, m->net.split != 0, m->obs_dim, net, a);
   a.obs_dim = m->obs_dim, a.out_dim = m->out_dim;
   for (int i = 0; i < SKU_TENSORS; i++) {
     if (!p[i]) return false;
@@ -199,7 +199,7 @@ int skyjo_vec_grad_norm(const float *const tensors[], const int64_t counts[], in
 int64_t skyjo_vec_mlp_packed_bytes(const skyjo_vec_mlp *m) {
   if (!m) return 0;
   size_t n = 0;
-  for (int k = 0; k < 8; k++) n += skp_piece_bytes(k, m->net.split != 0);
+  for (int k = 0; k < 8; k++) n += skp_piece_bytes(k, m->net.split != 0, skp_w1_ksteps(m->obs_dim));
   return (int64_t)n;
 }
 
@@ -209,9 +209,9 @@ int skyjo_vec_mlp_export(const skyjo_vec_mlp *m, void *dst_device, int64_t bytes
   DevGuard guard_(m->device_id);
   size_t at = 0;
   for (int k = 0; k < 8; k++) {
-    const size_t n = skp_piece_bytes(k, m->net.split != 0);
+    const size_t n = skp_piece_bytes(k, m->net.split != 0, skp_w1_ksteps(m->obs_dim));
     if (!n) continue;
-    HIPCHK(hipMemcpyAsync((uint8_t *)dst_device + at, (const uint8_t *)m->blob + skp_piece_offset(k, m->net.split != 0), n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync((uint8_t *)dst_device + at, (const uint8_t *)m->blob + skp_piece_offset(k, m->net.split != 0, skp_w1_ksteps(m->obs_dim)), n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     at += n;
   }
   return SKYJO_OK;
@@ -222,6 +222,8 @@ int skyjo_vec_mlp_forward_layout(const skyjo_vec_mlp *m, const void *records, in
   if (!m || !records || !out || n < 0 || record_bytes < 32 || (record_bytes & 15))
     return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_forward: bad argument");
   if (int rc = check_layout(layout)) return rc;
+  if (record_bytes < 16 * skp_w1_ksteps(m->obs_dim))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_forward: record_bytes must hold layer 1's 16 * (obs_dim / 16 + 1) columns");
   if (n == 0) return SKYJO_OK;
   DevGuard guard_(m->device_id);
   SkMlpDraw nodraw{};
@@ -245,6 +247,8 @@ int skyjo_vec_mlp_act_value_layout(skyjo_vec *h, const skyjo_vec_mlp *policy, co
   if (value && (policy->obs_dim != value->obs_dim || policy->device_id != value->device_id || policy->device_id != e.device_id ||
                 policy->net.split != value->net.split))
     return fail(SKYJO_E_INVALID, "policy and value net must share the observation size, the precision and the engine's device");
+  if ((int)e.L->rec_bytes < 16 * skp_w1_ksteps(policy->obs_dim))
+    return fail(SKYJO_E_INVALID, "skyjo_vec_mlp_act_value: the engine's records are shorter than the net's layer 1 (obs_dim)");
   if (n == 0) return SKYJO_OK;
   SkMlpDraw d{};
   d.enable = 1, d.mask_offset = e.L->Dp, d.no_masking = no_masking, d.seed = seed, d.ticket = ticket;

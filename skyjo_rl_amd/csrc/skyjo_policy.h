@@ -7,7 +7,11 @@
 #include <stdint.h>
 
 #define SKP_HIDDEN 256
-#define SKP_IN 32    // 31 observation features + a constant 1 that carries the first layer's bias
+#define SKP_IN 32    // the narrow nets' layer 1: up to 31 observation features + a constant 1 that carries the first layer's bias
+// A net of obs_dim inputs takes KS = obs_dim / 16 + 1 k-steps of 16 columns in layer 1 (skyjo_update.h: skp_w1_ksteps); the constant 1 is
+// column 16 KS - 1.  163 = 19 + 12 x 12: the direct observation of twelve players, KS = 11.  obs_dim > SKP_IN - 1: the wide kernels.
+#define SKP_MAX_OBS 163
+#define SKP_MAX_KS (SKP_MAX_OBS / 16 + 1)
 #define SKP_OUT 32   // up to 32 outputs (26 logits, or 1 value)
 #define SKP_WG 8     // wavefronts per workgroup: 8 x 32 games share one copy of the 256 x 256 layer in LDS
 #define SKP_GAMES_PER_WG (32 * SKP_WG)
@@ -24,7 +28,7 @@ struct SkMlpDraw {
 };
 
 struct SkMlpDev {
-  const uint4 *w1;   // [8 m-tiles][2 k-steps][64 lanes] fragments, natural k order (k = feature; k = 31 carries the bias)
+  const uint4 *w1;   // [8 m-tiles][KS k-steps][64 lanes] fragments, natural k order (k = feature; k = 16 KS - 1 carries the bias)
   const uint4 *w2;   // [8][16][64] fragments, accumulator k order
   const uint4 *w3;   // [1][16][64]
   const float *b2;   // [256] bias of layer 2, times SKP_SCALE (bf16: + W 1 of the r-fold); the kernels read a lane's eight rows once per
@@ -46,6 +50,7 @@ struct SkMlpRecords {
 };
 
 // One launch of the policy net (nets == 2: policy and value branch over the same records, grid.y = 2) in the nets'
-// precision.  e0 / e1: events recorded around the kernel (hipExtLaunchKernelGGL), or null.  Returns a hipError_t.
+// precision.  e0 / e1: events recorded around the kernel (hipExtLaunchKernelGGL), or null.  Returns a hipError_t
+// (hipErrorInvalidValue, nothing launched: layer 1's 16 KS bytes do not lie inside a record).
 int sk_launch_mlp(const SkMlpDev &a, const SkMlpDev &b, int nets, const SkMlpRecords &r, float *out_a, const SkMlpDraw &draw,
                   float *out_b, hipStream_t s, hipEvent_t e0, hipEvent_t e1);

@@ -33,6 +33,7 @@ typedef float skp_f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t skp_u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) float *skp_lds_f32;  // (an LDS pointer that stays one: ds_read, not flat_load)
 #define SKP_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
+#define SKP_GAP_END __builtin_amdgcn_sched_barrier(0)  // closes a "gap" of the software pipelines below: nothing moves across
 #define SKP_LDS32(p) ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(p))  // the LDS offset of a __shared__ object
 
 __device__ __forceinline__ skp_bf16x8 skp_frag(const uint4 *p) {
@@ -87,6 +88,86 @@ __device__ __forceinline__ void skp_inputs(const SkMlpRecords &R, const uint32_t
       const float v0 = (float)(int8_t)(ob[k0 >> 2] >> ((k0 & 3) * 8)), v1 = (float)(int8_t)(ob[k1 >> 2] >> ((k1 & 3) * 8));
       x[s][j] = (__bf16)(h ? v1 : v0);
     }
+}
+
+// ---- wide nets (obs_dim > 31, the direct observation: KS = obs_dim / 16 + 1 k-steps of layer 1, K = 16 KS columns) ----
+// The wide kernels (k_net_bf16_wide, k_net_split_wide) are the narrow ones with another layer 1; everything behind it is the code the narrow
+// kernels run.  What differs:
+//   * KS input fragments instead of two.  A kernel is compiled for up to MKS k-steps (5: up to 79 inputs, i.e. five players; 11: all) and
+//     runs all MKS as straight-line code - a k-step beyond KS repeats k-step KS - 1's loads against an input fragment of zeros (every byte
+//     from obs_dim on is masked to 0), so there is no branch per k-step for the loads to queue behind.
+//   * Layer 1's weights - 8 KS KB, twice that float32-grade: up to 88 / 176 KB - are read fragment by fragment from memory where they are
+//     used, not kept in LDS: the slot beside layers 2 / 3 holds KS = 2 (the wide kernels leave it out: 144 / 128 KB of LDS), and staging
+//     one m-tile at a time through it would trade the vector memory pipe's 64 bytes per clock for LDS's 128 at two workgroup barriers per tile -
+//     every wavefront needs every fragment either way.  The piece stays L2-resident: all workgroups read the same 8 KS KB.
+
+// this lane's bytes of its game's record - 16 s + 8 h .. + 7 of piece s < KS, inside the record: 16 KS <= rec_bytes (sk_launch_mlp) - as two
+// words per k-step, as they lie there (zeros beyond the last game); nothing consumes them here, so a request for the next batch stays in flight
+template <int MKS>
+__device__ __forceinline__ void skp_record_load_wide(const SkMlpRecords &R, const long long g, const int h, const int KS, uint32_t (&ob)[2 * MKS]) {
+#pragma unroll
+  for (int s = 0; s < MKS; s++) {
+    uint2 q = {0, 0};
+    if (g < R.n) q = *(const uint2 *)((const uint8_t *)skp_piece(R, g, min(s, KS - 1)) + 8 * h);
+    ob[2 * s] = q.x, ob[2 * s + 1] = q.y;
+  }
+}
+// input fragment s: columns 16 s + 8 h .. + 7, int8 -> bf16 (exact).  Everything from byte obs_dim on enters as 0 - the action byte, the pad, the
+// mask, a k-step beyond KS - but column K - 1 (k-step KS - 1, upper half, last value), the constant 1 against b1.  The masks depend on obs_dim
+// and s alone (scalar); a lane picks its half's.
+__device__ __forceinline__ skp_bf16x8 skp_input_wide(const int obs_dim, const int KS, const int s, const int h, const uint32_t w0, const uint32_t w1) {
+  uint32_t w[2] = {w0, w1};
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    const int la = obs_dim - (16 * s + 4 * i), lb = la - 8;  // observation bytes in this word of the lower / upper half
+    const uint32_t ma = la >= 4 ? 0xffffffffu : la <= 0 ? 0u : (1u << (8 * la)) - 1u, mb = lb >= 4 ? 0xffffffffu : lb <= 0 ? 0u : (1u << (8 * lb)) - 1u;
+    w[i] &= h ? mb : ma;
+  }
+  const uint32_t one = s == KS - 1 ? 0x01000000u : 0u;
+  w[1] |= h ? one : 0u;
+  skp_bf16x8 x;
+#pragma unroll
+  for (int j = 0; j < 8; j++) x[j] = (__bf16)(float)(int8_t)(w[j >> 2] >> ((j & 3) * 8));
+  return x;
+}
+// where layer 1's fragment (m-tile t, k-step s) of this lane lies, counted in fragments
+__device__ __forceinline__ size_t skp_w1_at(const int t, const int s, const int KS, const int lane) { return ((size_t)t * KS + min(s, KS - 1)) * 64 + lane; }
+// bf16: output tile t of layer 1 on input fragments built once per batch (4 MKS registers)
+template <int MKS>
+__device__ __forceinline__ skp_f32x16 skp_l1_wide_bf16(const SkMlpDev &net, const int t, const int KS, const int lane, const skp_bf16x8 (&x)[MKS]) {
+  skp_f32x16 acc = skp_zero();
+#pragma unroll
+  for (int s = 0; s < MKS; s++) acc = SKP_MFMA(skp_frag(net.w1 + skp_w1_at(t, s, KS, lane)), x[s], acc);
+  return acc;
+}
+// float32-grade: output tiles t and t + 1 together - lo and hi weights x the one exact input fragment, in the narrow kernel's order.  That kernel
+// has no room for MKS input fragments (h1h + h1l fill 128 registers by the last tile): a fragment is rebuilt from the record's two words where it
+// is used, once per pair of tiles - two accumulators are what the narrow layer 1 holds too.
+template <int MKS>
+__device__ __forceinline__ void skp_l1_pair_split(const SkMlpDev &net, const int obs_dim, const int t, const int KS, const int lane, const int h,
+                                                  const uint32_t (&ob)[2 * MKS], skp_f32x16 &acc0, skp_f32x16 &acc1) {
+  acc0 = skp_zero(), acc1 = skp_zero();
+  // (Left alone the compiler requests all 4 MKS fragments at once - 176 registers - and spills.  A scheduling barrier closes every k-step:
+  // tile t's two fragments are requested a k-step ahead, tile t + 1's at the start of their own - in front of the input fragment's
+  // conversion and tile t's two MFMAs; four a k-step ahead were eight registers more than MKS = 11 has.)
+  skp_bf16x8 f[4], n[2];
+  f[0] = skp_frag(net.w1l + skp_w1_at(t, 0, KS, lane)), f[1] = skp_frag(net.w1 + skp_w1_at(t, 0, KS, lane));
+#pragma unroll
+  for (int s = 0; s < MKS; s++) {
+    const size_t a1 = skp_w1_at(t + 1, s, KS, lane);
+    f[2] = skp_frag(net.w1l + a1), f[3] = skp_frag(net.w1 + a1);
+    if (s + 1 < MKS) {
+      const size_t a0 = skp_w1_at(t, s + 1, KS, lane);
+      n[0] = skp_frag(net.w1l + a0), n[1] = skp_frag(net.w1 + a0);
+    }
+    const skp_bf16x8 xs = skp_input_wide(obs_dim, KS, s, h, ob[2 * s], ob[2 * s + 1]);
+    acc0 = SKP_MFMA(f[0], xs, acc0);
+    acc0 = SKP_MFMA(f[1], xs, acc0);
+    acc1 = SKP_MFMA(f[2], xs, acc1);
+    acc1 = SKP_MFMA(f[3], xs, acc1);
+    SKP_GAP_END;
+    f[0] = n[0], f[1] = n[1];
+  }
 }
 
 // What follows the last layer, for the 32 games of a wavefront: the outputs go to memory (out: float32 [n][out_dim], may be
@@ -217,7 +298,6 @@ __device__ __forceinline__ void skp_act_gap(SkpAct &a, const int i, const skp_f3
     a.hprev = ro;
   }
 }
-#define SKP_GAP_END __builtin_amdgcn_sched_barrier(0)
 
 // ------------------------------------------------------------------------------------------------------------------
 // bf16 mode (SKYJO_MLP_BF16): single bf16 weights and inter-layer activations, float32 accumulation.
@@ -270,10 +350,18 @@ __device__ __forceinline__ void skp_stage_bf16(const uint4 *w2s, const uint4 *w3
 
 // One batch of 256 games (32 per wavefront).  FIRST: the workgroup's first batch, which also brings the weights of layers 2 and 3
 // into LDS; `more`: another batch follows (its record is requested behind layer 1).
-template <bool FIRST>
+// NOB: the record words a lane holds - 8: the narrow net (k_net_bf16); 2 MKS > 8: a wide one (k_net_bf16_wide<MKS>), which has no w1s.
+template <bool FIRST, int NOB = 8>
 __device__ __forceinline__ void skp_batch_bf16(const SkMlpDev &net, const SkMlpRecords &R, float *const out, const SkMlpDraw &draw, uint4 *w2s,
                                                uint4 *w3s, uint4 *w1s, const long long batch, const bool more, const int lane, const int wave,
-                                               const int col, const int h, uint32_t (&ob)[8], uint32_t (&bq)[9]) {
+                                               const int col, const int h, uint32_t (&ob)[NOB], uint32_t (&bq)[9]) {
+  constexpr bool WIDE = NOB > 8;
+  constexpr int MKS = NOB / 2;
+  // (wide only.  Opaque: layer 1's masks and fragment offsets depend on obs_dim alone, and the compiler would keep them all - some hundred
+  // scalars - from before the batch loop on)
+  int obs_dim = R.obs_dim;
+  if constexpr (WIDE) asm volatile("" : "+s"(obs_dim));
+  const int KS = obs_dim / 16 + 1;
   SKP_STAMP_DECL;
   const long long g = (batch * SKP_WG + wave) * 32 + col;
   // ---- How a launch starts (stamped, EXPERIMENTS round 6, 24): the compute unit has ONE vector memory pipe, a 16-byte-per-lane load
@@ -288,29 +376,44 @@ __device__ __forceinline__ void skp_batch_bf16(const SkMlpDev &net, const SkMlpR
   skp_u32x4 stg[18];  // (a native vector type: HIP's uint4 is a struct of unions, and an array of them stays in scratch)
   float bf[9];
   if (FIRST) {
-    const skp_u32x4 s0 = *(const skp_u32x4 *)(net.w1 + (2 * wave) * 64 + lane), s1 = *(const skp_u32x4 *)(net.w1 + (2 * wave + 1) * 64 + lane);
+    skp_u32x4 s0, s1;
+    if constexpr (!WIDE) s0 = *(const skp_u32x4 *)(net.w1 + (2 * wave) * 64 + lane), s1 = *(const skp_u32x4 *)(net.w1 + (2 * wave + 1) * 64 + lane);
     // this lane's biases: output row 32 u + col of layer 2 (net.b2: float32 [256], scaled), row col of layer 3 (net.b3 is laid out
     // per lane and accumulator register: row (r & 3) + 8 (r >> 2) + 4 h' at [32 h'][r])
 #pragma unroll
     for (int u = 0; u < 8; u++) bf[u] = net.b2[32 * u + col];
     bf[8] = net.b3[(32 * ((col >> 2) & 1)) * 16 + (col & 3) + 4 * (col >> 3)];
-    *(skp_u32x4 *)(w1s + (2 * wave) * 64 + lane) = s0, *(skp_u32x4 *)(w1s + (2 * wave + 1) * 64 + lane) = s1;
-    SKP_STAMP(2);
-    __syncthreads();  // layer 1 is in LDS
-    SKP_STAMP(16);
+    if constexpr (!WIDE) {
+      *(skp_u32x4 *)(w1s + (2 * wave) * 64 + lane) = s0, *(skp_u32x4 *)(w1s + (2 * wave + 1) * 64 + lane) = s1;
+      SKP_STAMP(2);
+      __syncthreads();  // layer 1 is in LDS
+      SKP_STAMP(16);
+    }
   }
-  skp_bf16x8 x[2], w1f[16];
+  skp_bf16x8 x[WIDE ? MKS : 2], w1f[16];
+  if constexpr (!WIDE) {
 #pragma unroll
-  for (int k = 0; k < 16; k++) w1f[k] = skp_frag(w1s + k * 64 + lane);
+    for (int k = 0; k < 16; k++) w1f[k] = skp_frag(w1s + k * 64 + lane);
+  }
   skp_f32x16 acc3, cur, bias_next;
-  skp_inputs(R, ob, h, x);
+  if constexpr (WIDE) {
+#pragma unroll
+    for (int s = 0; s < MKS; s++) x[s] = skp_input_wide(obs_dim, KS, s, h, ob[2 * s], ob[2 * s + 1]);
+  } else {
+    skp_inputs(R, ob, h, x);
+  }
   SKP_STAMP(1 + 14 * (FIRST ? 0 : 1));
   // ---- layer 1: 31 (+1) -> 256, tanh (the bias rides in the product: feature 31 is 1); the result tiles become the 16
   // k-step fragments of layer 2.  Tile t + 1's two MFMAs sit in the first gaps of tile t's activations ----
   skp_bf16x8 h1[16];
   {
-    skp_f32x16 acc = SKP_MFMA(w1f[0], x[0], skp_zero());
-    acc = SKP_MFMA(w1f[1], x[1], acc);
+    skp_f32x16 acc;
+    if constexpr (WIDE) {
+      acc = skp_l1_wide_bf16<MKS>(net, 0, KS, lane, x);
+    } else {
+      acc = SKP_MFMA(w1f[0], x[0], skp_zero());
+      acc = SKP_MFMA(w1f[1], x[1], acc);
+    }
     SKP_GAP_END;
 #pragma unroll
     for (int t = 0; t < 8; t++) {
@@ -318,8 +421,12 @@ __device__ __forceinline__ void skp_batch_bf16(const SkMlpDev &net, const SkMlpR
       skp_f32x16 nxt;
 #pragma unroll
       for (int i = 0; i < 18; i++) {
-        if (t < 7 && i == 0) nxt = SKP_MFMA(w1f[2 * t + 2], x[0], skp_zero());
-        if (t < 7 && i == 1) nxt = SKP_MFMA(w1f[2 * t + 3], x[1], nxt);
+        if constexpr (WIDE) {  // (tile t + 1's MFMAs, their fragments from memory, in the first gap)
+          if (t < 7 && i == 0) nxt = skp_l1_wide_bf16<MKS>(net, t + 1, KS, lane, x);
+        } else {
+          if (t < 7 && i == 0) nxt = SKP_MFMA(w1f[2 * t + 2], x[0], skp_zero());
+          if (t < 7 && i == 1) nxt = SKP_MFMA(w1f[2 * t + 3], x[1], nxt);
+        }
         // the wavefront's 18 KiB of layers 2 / 3: piece j requested in tile j / 3, written to LDS two tiles on.  (All eighteen requested
         // up front - eight wavefronts at once, right behind their barrier - kept every wavefront 2 500 cycles in the queue of the pipe.)
         if (FIRST && t < 6 && (i == 2 || i == 7 || i == 12)) {
@@ -348,7 +455,11 @@ __device__ __forceinline__ void skp_batch_bf16(const SkMlpDev &net, const SkMlpR
   }
   if (FIRST) __syncthreads();  // everybody's share of the weights is in LDS
   // the next batch's record, requested now: it arrives while layers 2 and 3 run
-  if (more) skp_record_load(R, ((batch + 1) * SKP_WG + wave) * 32 + col, ob);
+  if constexpr (WIDE) {
+    if (more) skp_record_load_wide<MKS>(R, ((batch + 1) * SKP_WG + wave) * 32 + col, h, KS, ob);
+  } else {
+    if (more) skp_record_load(R, ((batch + 1) * SKP_WG + wave) * 32 + col, ob);
+  }
   SKP_STAMP(4 + 14 * (FIRST ? 0 : 1));
   // ---- layers 2 and 3 ----
   const uint32_t oq[4] = {h ? 0u : 0x3f803f80u, 0u, 0u, 0u};  // ones in k = 0, 1
@@ -411,6 +522,40 @@ __global__ __launch_bounds__(64 * SKP_WG) __attribute__((amdgpu_waves_per_eu(2, 
     int lane_o = lane;
     asm volatile("" : "+v"(lane_o));
     skp_batch_bf16<false>(net, R, out, draw, w2s, w3s, w1s, batch, pass + 1 < passes, lane_o, wave, lane_o & 31, lane_o >> 5, ob, bq);
+  }
+  SKP_RSTAMP(30);
+}
+// obs_dim > 31, up to MKS k-steps of layer 1 (skp_l1_wide_bf16).  The body is k_net_bf16's, copied: shared through a function, the narrow kernel's
+// instructions came out in another order (EXPERIMENTS, wide nets).
+template <int MKS>
+__global__ __launch_bounds__(64 * SKP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_net_bf16_wide(const SkMlpArgs A) {
+  __shared__ uint4 w2s[8 * 16 * 64];  // the 256 x 256 layer (128 KB)
+  __shared__ uint4 w3s[16 * 64];      // layer 3 (16 KB)
+  uint4 *const w1s = nullptr;         // (layer 1 comes from memory: 144 KB)
+  // (the branch's descriptor is read from the kernel-argument segment by index: one set of scalar registers, not two and a select)
+  const SkMlpDev &net = A.net[blockIdx.y];
+  float *const out = A.out[blockIdx.y];
+  const SkMlpRecords &R = A.R;
+  const int passes = A.passes;
+  SkMlpDraw draw = A.draw;
+  draw.enable = blockIdx.y ? 0 : A.draw.enable;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), col = lane & 31, h = lane >> 5;
+  SKP_STAMP_DECL;
+  SKP_STAMP(0);
+  SKP_RSTAMP(29);
+  uint32_t ob[2 * MKS];
+  skp_record_load_wide<MKS>(R, ((long long)blockIdx.x * passes * SKP_WG + wave) * 32 + col, h, R.obs_dim / 16 + 1, ob);
+  uint32_t bq[9];
+  skp_batch_bf16<true, 2 * MKS>(net, R, out, draw, w2s, w3s, w1s, (long long)blockIdx.x * passes, passes > 1, lane, wave, col, h, ob, bq);
+#pragma unroll 1
+  for (int pass = 1; pass < passes; pass++) {
+    const long long batch = (long long)blockIdx.x * passes + pass;
+    if (batch * SKP_GAMES_PER_WG >= R.n) break;  // (uniform: a workgroup's later batches may lie beyond the last game)
+    // (everything that depends on the lane alone is the same in every batch: the compiler would compute it all ahead of the loop
+    // and, 256 registers being in use, spill it - a private segment costs the launch ~ 1 us.  The lane number is opaque in here.)
+    int lane_o = lane;
+    asm volatile("" : "+v"(lane_o));
+    skp_batch_bf16<false, 2 * MKS>(net, R, out, draw, w2s, w3s, w1s, batch, pass + 1 < passes, lane_o, wave, lane_o & 31, lane_o >> 5, ob, bq);
   }
   SKP_RSTAMP(30);
 }
@@ -728,9 +873,165 @@ __global__ __launch_bounds__(64 * SKP_WG) __attribute__((amdgpu_waves_per_eu(2, 
   }
   SKP_RSTAMP(30);
 }
+// obs_dim > 31, up to MKS k-steps of layer 1.  The body is k_net_split's, copied (k_net_bf16_wide says why), with layer 1 in pairs of tiles.
+template <int MKS>
+__global__ __launch_bounds__(64 * SKP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_net_split_wide(const SkMlpArgs A) {
+  __shared__ uint4 ring[3 * SKP_TILE_U4];  // three output tiles of the 256 x 256 layer (96 KB)
+  __shared__ uint4 w3s[2 * 16 * 64];       // layer 3, [hi, lo][16 k-steps][64 lanes] (32 KB)
+  // (layer 1 comes from memory: 128 KB)
+  // (the branch's descriptor is read from the kernel-argument segment by index: one set of scalar registers, not two and a select)
+  const SkMlpDev &net = A.net[blockIdx.y];
+  float *const out = A.out[blockIdx.y];
+  const SkMlpRecords &R = A.R;
+  const int passes = A.passes;
+  SkMlpDraw draw = A.draw;
+  draw.enable = blockIdx.y ? 0 : A.draw.enable;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), col = lane & 31, h = lane >> 5;
+  SKP_STAMP_DECL;
+  SKP_STAMP(0);
+  SKP_RSTAMP(29);
+  const int KS = R.obs_dim / 16 + 1;
+  float bf[5];
+  {
+    // what stays in LDS for the whole launch (layer 3) and the first two tiles of the ring; the biases of layers 2 / 3 stay in
+    // registers (bq) and enter as MFMAs - no LDS left for them, and no load inside the pipeline (EXPERIMENTS round 6, 24)
+#pragma unroll
+    for (int j = 0; j < 4; j++) bf[j] = net.b2[32 * (j + 4 * h) + col];
+    bf[4] = net.b3[(32 * ((col >> 2) & 1)) * 16 + (col & 3) + 4 * (col >> 3)];
+    skp_u32x4 t3[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) t3[j] = *(const skp_u32x4 *)(((wave >> 2) ? net.w3l : net.w3) + (wave & 3) * 256 + j * 64 + lane);
+#pragma unroll
+    for (int j = 0; j < 4; j++) *(skp_u32x4 *)(w3s + wave * 256 + j * 64 + lane) = t3[j];
+#pragma unroll
+    for (int tile = 0; tile < 2; tile++) {
+      SkpStage a, b;
+      skp_stage_load(net, tile, wave, lane, 0, a);
+      skp_stage_load(net, tile, wave, lane, 1, b);
+#pragma unroll
+      for (int k = 0; k < 2; k++) skp_stage_store(ring + tile * SKP_TILE_U4 + lane, wave, 0, k, a), skp_stage_store(ring + tile * SKP_TILE_U4 + lane, wave, 1, k, b);
+    }
+  }
+  __syncthreads();
+  // this lane's bias values as bf16 pairs (hi, lo: exact to 2^-17): skp_bias_split
+  uint32_t bq[5];
+#pragma unroll
+  for (int j = 0; j < 5; j++) bq[j] = skp_pk(bf[j], bf[j] - __uint_as_float(skp_pk(bf[j], 0.f) << 16));
+  bq[4] = h ? 0u : bq[4];
+#pragma unroll 1
+  for (int pass = 0; pass < passes; pass++) {
+    const long long batch = (long long)blockIdx.x * passes + pass;
+    if (batch * SKP_GAMES_PER_WG >= R.n && pass > 0) break;
+    const bool more = pass + 1 < passes && (batch + 1) * SKP_GAMES_PER_WG < R.n;  // this workgroup has another batch
+    const long long g = (batch * SKP_WG + wave) * 32 + col;
+    // (the record is requested where its batch starts, not a batch ahead as in k_net_split: 2 MKS more registers through layers 2 / 3 are
+    // more than that kernel has - one round trip to memory per batch instead)
+    uint32_t ob[2 * MKS];
+    skp_record_load_wide<MKS>(R, g, h, KS, ob);
+    // this batch's tile u lives in ring slot (8 pass + u) % 3: rot[u % 3] is this lane's fragment of its k-step 0 (hi)
+    uint4 *rot[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) rot[k] = ring + ((8 * pass + k) % 3) * SKP_TILE_U4 + lane;
+    // ---- layer 1: (hi + lo) weights x exact inputs, two output tiles at a time (skp_l1_pair_split: their 4 MKS MFMAs in one burst, then the
+    // two tiles' activations); layer 2's first chain (output tile 0) follows it k-step by k-step: tile t - 1's two
+    // k-steps between the activations of tile t.  Tile 2 travels into the ring on the side ----
+    SKP_STAMP(1 + 14 * (pass > 0));
+    skp_bf16x8 h1h[16], h1l[16];
+    skp_f32x16 cur = skp_zero();
+    {
+      // (layer 1's addresses depend on the lane alone and are the same in every batch: left alone the compiler computes them all - 32 MKS
+      // 64-bit pairs - ahead of the batch loop and spills them.  The lane number is opaque in here, as in k_net_bf16's later batches.)
+      // (So do its masks and offsets on obs_dim: some hundred scalars.)
+      int lane_o = lane, obs_o = R.obs_dim;
+      asm volatile("" : "+v"(lane_o));
+      asm volatile("" : "+s"(obs_o));
+      const int KS_o = obs_o / 16 + 1;
+      skp_f32x16 acc, nxt;
+      skp_l1_pair_split<MKS>(net, obs_o, 0, KS_o, lane_o, lane_o >> 5, ob, acc, nxt);
+      SKP_GAP_END;
+      SkpStage st;
+#pragma unroll
+      for (int t = 0; t < 8; t++) {
+        SkpActS act;
+        skp_bf16x8 c0h, c0l, c1h, c1l;
+        const int ks0 = 2 * (t - 1), ks1 = ks0 + 1;
+#pragma unroll
+        for (int gp = 0; gp < SKP_L1_GAPS; gp++) {
+          if (t >= 1) {
+            if (gp == 2) c0h = skp_frag(rot[0] + ks0 * 64), c0l = skp_frag(rot[0] + 1024 + ks0 * 64);
+            if (gp == 8) c1h = skp_frag(rot[0] + ks1 * 64), c1l = skp_frag(rot[0] + 1024 + ks1 * 64);
+            if (gp >= 6 && gp < 9) cur = SKP_MFMA(gp == 7 ? c0l : c0h, gp == 6 ? h1l[ks0] : h1h[ks0], cur);
+            if (gp >= 12 && gp < 15) cur = SKP_MFMA(gp == 13 ? c1l : c1h, gp == 12 ? h1l[ks1] : h1h[ks1], cur);
+          }
+          // tile 2's two halves: requested in tiles 0 / 4 of layer 1, written in tiles 3 / 7
+          if ((t == 0 || t == 4) && gp == 10) skp_stage_load(net, 2, wave, lane, t == 4, st);
+          if ((t == 3 || t == 7) && (gp == 16 || gp == 17)) skp_stage_store(rot[2], wave, t == 7, gp - 16, st);
+          skp_act_split_gap<1, 0>(act, gp, acc);
+          SKP_GAP_END;
+        }
+        h1h[2 * t] = skp_frag4((const uint32_t(&)[4])act.hi[0]), h1h[2 * t + 1] = skp_frag4((const uint32_t(&)[4])act.hi[4]);
+        h1l[2 * t] = skp_frag4((const uint32_t(&)[4])act.lo[0]), h1l[2 * t + 1] = skp_frag4((const uint32_t(&)[4])act.lo[4]);
+        if (t & 1) {
+          if (t < 7) {
+            skp_l1_pair_split<MKS>(net, obs_o, t + 1, KS_o, lane_o, lane_o >> 5, ob, acc, nxt);
+            SKP_GAP_END;
+          }
+        } else {
+          acc = nxt;
+        }
+      }
+#pragma unroll
+      for (int ks = 14; ks < 16; ks++) {
+        const skp_bf16x8 ch = skp_frag(rot[0] + ks * 64), cl = skp_frag(rot[0] + 1024 + ks * 64);
+        cur = SKP_MFMA(ch, h1l[ks], cur);
+        cur = SKP_MFMA(cl, h1h[ks], cur);
+        cur = SKP_MFMA(ch, h1h[ks], cur);
+      }
+      cur = skp_bias_split(bq, 0, h, cur);
+    }
+    SKP_STAMP(3 + 14 * (pass > 0));
+    // ---- layers 2 and 3.  One barrier per stage: everybody's share of the tile that is read two stages on has been written, and
+    // everybody is through with the slot that the next stage refills ----
+    skp_f32x16 acc3 = skp_bias_split(bq, 8, h, skp_zero());
+    SKP_GAP_END;
+    __syncthreads();
+    skp_bf16x8 ah = skp_frag(rot[1]), al = skp_frag(rot[1] + 1024);
+    SKP_STAMP(5 + 14 * (pass > 0));
+    skp_stage_split<0>(net, rot, w3s, lane, wave, h, h1h, h1l, cur, acc3, ah, al, bq);
+    __syncthreads();
+    SKP_STAMP(6 + 14 * (pass > 0));
+    skp_stage_split<1>(net, rot, w3s, lane, wave, h, h1h, h1l, cur, acc3, ah, al, bq);
+    __syncthreads();
+    SKP_STAMP(7 + 14 * (pass > 0));
+    skp_stage_split<2>(net, rot, w3s, lane, wave, h, h1h, h1l, cur, acc3, ah, al, bq);
+    __syncthreads();
+    SKP_STAMP(8 + 14 * (pass > 0));
+    skp_stage_split<3>(net, rot, w3s, lane, wave, h, h1h, h1l, cur, acc3, ah, al, bq);
+    __syncthreads();
+    SKP_STAMP(9 + 14 * (pass > 0));
+    skp_stage_split<4>(net, rot, w3s, lane, wave, h, h1h, h1l, cur, acc3, ah, al, bq);
+    __syncthreads();
+    SKP_STAMP(10 + 14 * (pass > 0));
+    skp_stage_split<5>(net, rot, w3s, lane, wave, h, h1h, h1l, cur, acc3, ah, al, bq);
+    __syncthreads();
+    SKP_STAMP(11 + 14 * (pass > 0));
+    skp_stage_split<6>(net, rot, w3s, lane, wave, h, h1h, h1l, cur, acc3, ah, al, bq);
+    __syncthreads();
+    SKP_STAMP(12 + 14 * (pass > 0));
+    skp_stage_split<7>(net, rot, w3s, lane, wave, h, h1h, h1l, cur, acc3, ah, al, bq);
+    SKP_STAMP(13 + 14 * (pass > 0));
+    skp_finish(acc3, lane, g, R, net.out_dim, out, draw);
+    SKP_STAMP(14 + 14 * (pass > 0));
+  }
+  SKP_RSTAMP(30);
+}
 
 int sk_launch_mlp(const SkMlpDev &a, const SkMlpDev &b, int nets, const SkMlpRecords &r, float *out_a, const SkMlpDraw &draw,
                   float *out_b, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+  const int KS = r.obs_dim / 16 + 1;
+  const bool wide = r.obs_dim > SKP_IN - 1;
+  // (a wide kernel reads the 16 KS bytes of layer 1's columns from every record)
+  if (r.obs_dim < 1 || r.obs_dim > SKP_MAX_OBS || (wide && 16 * KS > r.rec_bytes)) return (int)hipErrorInvalidValue;
   const long long batches = (r.n + SKP_GAMES_PER_WG - 1) / SKP_GAMES_PER_WG;
   // one round of workgroups where the batch allows it: a workgroup owns a CU (its LDS), 256 CUs, `nets` workgroups per batch
   int passes = (int)((batches * nets + 255) / 256);
@@ -739,9 +1040,10 @@ int sk_launch_mlp(const SkMlpDev &a, const SkMlpDev &b, int nets, const SkMlpRec
   const dim3 grid((unsigned)((batches + passes - 1) / passes), (unsigned)nets), block(64 * SKP_WG);
   SkMlpArgs A;
   A.net[0] = a, A.net[1] = b, A.out[0] = out_a, A.out[1] = out_b, A.R = r, A.draw = draw, A.passes = passes;
+  static_assert(SKP_MAX_KS == 11, "the wide kernels are compiled for up to 5 and up to 11 k-steps of layer 1");
   if (a.split)
-    hipExtLaunchKernelGGL(k_net_split, grid, block, 0, s, e0, e1, 0, A);
+    hipExtLaunchKernelGGL(!wide ? k_net_split : KS <= 5 ? k_net_split_wide<5> : k_net_split_wide<SKP_MAX_KS>, grid, block, 0, s, e0, e1, 0, A);
   else
-    hipExtLaunchKernelGGL(k_net_bf16, grid, block, 0, s, e0, e1, 0, A);
+    hipExtLaunchKernelGGL(!wide ? k_net_bf16 : KS <= 5 ? k_net_bf16_wide<5> : k_net_bf16_wide<SKP_MAX_KS>, grid, block, 0, s, e0, e1, 0, A);
   return (int)hipGetLastError();
 }

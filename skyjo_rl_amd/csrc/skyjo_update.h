@@ -10,7 +10,8 @@
 //     the rounded weights of a row in double in ascending k.
 // (b) k_mlp_update<ADAM>: SKU_BLOCKS workgroups of SKU_THREADS threads, ONE launch.  Workgroup u < 8 owns the hidden rows 32 u .. 32 u + 31
 //     (the m-tile u of both hidden layers): thread t packs the W2 fragment (u, ks = t / 64, lane = t % 64) - its eight k are two
-//     contiguous float4s of the row, acc_k's order - the first 128 threads also pack a W1 fragment (natural k order, k = 31 is b1), and
+//     contiguous float4s of the row, acc_k's order - the first 64 KS threads also pack a W1 fragment (natural k order, k = 16 KS - 1 is b1;
+//     KS = skp_w1_ksteps(obs_dim) k-steps, at most 11 x 64 = 704 of the 1 024), and
 //     after a barrier one lane per row forms b2's entry: in bf16 mode it walks its row's 256 weights, which its own workgroup has just
 //     written.  Workgroup 8 owns layer 3 the same way and spreads the 32 row biases over b3's accumulator layout.  A thread that owns
 //     an element reads p, g, m, v once, writes p, m, v once and packs the new p from its registers; every store to the blob is a whole
@@ -25,7 +26,7 @@
 
 #define SKU_THREADS 1024  // one W2 (or W3) fragment per thread of a workgroup: 16 k-steps x 64 lanes
 #define SKU_BLOCKS 9      // 8 m-tiles of the hidden layers + layer 3
-#define SKU_W1_FRAGS (8 * 2 * 64)
+#define SKU_W1_FRAGS(ks) (8 * (ks) * 64)  // layer 1's piece: ks = skp_w1_ksteps(obs_dim) k-steps of 16 columns
 #define SKU_W2_FRAGS (8 * 16 * 64)
 #define SKU_W3_FRAGS (16 * 64)
 #define SKU_TENSORS 6     // w1, b1, w2, b2, w3, b3
@@ -55,11 +56,15 @@ __device__ inline uint16_t skp_hi(float v, bool split) { return split ? skp_bf16
 
 // element j of the fragment of lane l: which k it holds.  Layer 1 in natural order (the kernel builds that operand from the record
 // itself), layers 2 and 3 in the order the accumulators of the layer before come out (hh = l >> 5)
+// Layer 1 takes KS = obs_dim / 16 + 1 k-steps (at least the narrow nets' two), K = 16 KS columns: column k < obs_dim is feature k, column K - 1
+// carries b1 against a constant 1, the columns between are zero.  obs_dim <= 31: KS = 2 and the bias in column 31; 47: K = 48, the bias in the
+// last free column; 48: KS = 4.
+__host__ __device__ inline int skp_w1_ksteps(int obs_dim) { return obs_dim < 16 ? 2 : obs_dim / 16 + 1; }
 __device__ inline int skp_w1_k(int s, int hh, int j) { return 16 * s + 8 * hh + j; }
 __device__ inline int skp_acc_k(int ks, int hh, int j) { return 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * hh + (j & 3); }
 __device__ inline int skp_row(int u, int l) { return 32 * u + (l & 31); }
 // where a fragment lies, counted in fragments of 8 values
-__device__ inline size_t skp_w1_frag(int u, int s, int l) { return ((size_t)u * 2 + s) * 64 + l; }
+__device__ inline size_t skp_w1_frag(int u, int s, int l, int ks) { return ((size_t)u * ks + s) * 64 + l; }
 __device__ inline size_t skp_w2_frag(int u, int ks, int l) { return ((size_t)u * 16 + ks) * 64 + l; }
 __device__ inline size_t skp_w3_frag(int ks, int l) { return (size_t)ks * 64 + l; }
 // b3 lies in accumulator layout, [64 lanes][16 registers]: the output row of register r of a lane of half hh
@@ -74,22 +79,23 @@ __device__ inline float skp_bias_sum(float bias, const float *row, bool scaled, 
 }
 
 // The pieces of the blob, in the order skyjo_vec_mlp_export writes them: w1, w2, w3, b2, b3, w1l, w2l, w3l (bytes; the *l pieces are
-// empty in bf16 mode).  In a skyjo_vec_mlp's blob each starts at a 256-byte boundary: skp_piece_offset, piece 8 being the blob's size.
-__host__ __device__ inline size_t skp_piece_bytes(int piece, bool split) {
+// empty in bf16 mode; ks: layer 1's k-steps, skp_w1_ksteps).  In a skyjo_vec_mlp's blob each starts at a 256-byte boundary:
+// skp_piece_offset, piece 8 being the blob's size.
+__host__ __device__ inline size_t skp_piece_bytes(int piece, bool split, int ks) {
   switch (piece) {
-    case 0: return (size_t)SKU_W1_FRAGS * 16;
+    case 0: return (size_t)SKU_W1_FRAGS(ks) * 16;
     case 1: return (size_t)SKU_W2_FRAGS * 16;
     case 2: return (size_t)SKU_W3_FRAGS * 16;
     case 3: return (size_t)SKP_HIDDEN * 4;
     case 4: return (size_t)64 * 16 * 4;
-    case 5: return split ? (size_t)SKU_W1_FRAGS * 16 : 0;
+    case 5: return split ? (size_t)SKU_W1_FRAGS(ks) * 16 : 0;
     case 6: return split ? (size_t)SKU_W2_FRAGS * 16 : 0;
     default: return split ? (size_t)SKU_W3_FRAGS * 16 : 0;
   }
 }
-__host__ __device__ inline size_t skp_piece_offset(int piece, bool split) {
+__host__ __device__ inline size_t skp_piece_offset(int piece, bool split, int ks) {
   size_t o = 0;
-  for (int k = 0; k < piece; k++) o += (skp_piece_bytes(k, split) + 255) & ~(size_t)255;
+  for (int k = 0; k < piece; k++) o += (skp_piece_bytes(k, split, ks) + 255) & ~(size_t)255;
   return o;
 }
 
@@ -131,14 +137,15 @@ struct SkUpdArgs {
 };
 
 // both views of a blob, from its base: the net kernels' (read only; no low halves in bf16 mode) and k_mlp_update's
-inline void skp_blob_views(void *blob, bool split, SkMlpDev &net, SkUpdArgs &a) {
+inline void skp_blob_views(void *blob, bool split, int obs_dim, SkMlpDev &net, SkUpdArgs &a) {
   uint8_t *b = (uint8_t *)blob;
-  net.w1 = a.f1 = (uint4 *)(b + skp_piece_offset(0, split)), net.w2 = a.f2 = (uint4 *)(b + skp_piece_offset(1, split));
-  net.w3 = a.f3 = (uint4 *)(b + skp_piece_offset(2, split));
-  net.b2 = a.c2 = (float *)(b + skp_piece_offset(3, split)), net.b3 = a.c3 = (float *)(b + skp_piece_offset(4, split));
-  net.w1l = a.g1 = split ? (uint4 *)(b + skp_piece_offset(5, split)) : nullptr;
-  net.w2l = a.g2 = split ? (uint4 *)(b + skp_piece_offset(6, split)) : nullptr;
-  net.w3l = a.g3 = split ? (uint4 *)(b + skp_piece_offset(7, split)) : nullptr;
+  const int ks = skp_w1_ksteps(obs_dim);
+  net.w1 = a.f1 = (uint4 *)(b + skp_piece_offset(0, split, ks)), net.w2 = a.f2 = (uint4 *)(b + skp_piece_offset(1, split, ks));
+  net.w3 = a.f3 = (uint4 *)(b + skp_piece_offset(2, split, ks));
+  net.b2 = a.c2 = (float *)(b + skp_piece_offset(3, split, ks)), net.b3 = a.c3 = (float *)(b + skp_piece_offset(4, split, ks));
+  net.w1l = a.g1 = split ? (uint4 *)(b + skp_piece_offset(5, split, ks)) : nullptr;
+  net.w2l = a.g2 = split ? (uint4 *)(b + skp_piece_offset(6, split, ks)) : nullptr;
+  net.w3l = a.g3 = split ? (uint4 *)(b + skp_piece_offset(7, split, ks)) : nullptr;
   net.split = a.split = split ? 1 : 0;
 }
 
@@ -217,13 +224,14 @@ __global__ __launch_bounds__(SKU_THREADS) void k_mlp_update(SkUpdArgs a) {
 #pragma unroll
     for (int j = 0; j < 8; j++) x[j] = skp_scaled(x[j]);
     sku_store_frag(x, split, true, a.f2, a.g2, skp_w2_frag(u, ks, l));
-    if (t < 128) {  // (ks is the k-step s of layer 1 here)
+    const int ks1 = skp_w1_ksteps(a.obs_dim);
+    if (t < 64 * ks1) {  // (ks is the k-step s of layer 1 here)
 #pragma unroll
       for (int j = 0; j < 8; j++) {
         const int k = skp_w1_k(ks, hh, j);
-        x[j] = skp_scaled(k < a.obs_dim ? sku_elem<ADAM>(a, 0, (size_t)m * a.obs_dim + k, coef) : (k == SKP_IN - 1 ? sku_elem<ADAM>(a, 1, m, coef) : 0.f));
+        x[j] = skp_scaled(k < a.obs_dim ? sku_elem<ADAM>(a, 0, (size_t)m * a.obs_dim + k, coef) : (k == 16 * ks1 - 1 ? sku_elem<ADAM>(a, 1, m, coef) : 0.f));
       }
-      sku_store_frag(x, split, false, a.f1, a.g1, skp_w1_frag(u, ks, l));
+      sku_store_frag(x, split, false, a.f1, a.g1, skp_w1_frag(u, ks, l, ks1));
     }
     __syncthreads();  // the workgroup's rows of w2 are written: bf16 mode sums them
     if (t < 32) {
