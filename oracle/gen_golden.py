@@ -39,6 +39,12 @@ inputs -> outputs of the hot path:
                    _calc_final_rewards on chosen end hands for N = 1 .. 12 under the penalties 2, 1.3, 1/3 and 0.01, and
                    _calc_final_rewards on arbitrary float64 score vectors (gen_scoring; tests/test_scoring_order.py)
 
+  late_boards_*.npz the reference on boards that random play never reaches (gen_late_boards): for N in {1, 2, 3, 4, 5, 12} in both
+                   observation modes, boards of the three families of tests/board_inject.py (several refunded columns, one or two
+                   actions from the end, open equal columns that were never collapsed) - seeded-random legal play to the episode's
+                   end, and one step of each of the 26 actions from a fresh copy (tests/test_oracle_golden.py,
+                   tests/test_gpu_late_boards.py)
+
 The fixtures are data (inputs and expected outputs) - no reference source text is stored.
 """
 import itertools
@@ -708,7 +714,129 @@ def gen_scoring(seed=5, e_small=14, e_large=24, f_rows=8):
     return size
 
 
+LATE_BOARDS = {1: 25, 2: 25, 3: 25, 4: 25, 5: 25, 12: 25}  # boards per file: one pass through board_inject.RECIPES
+LATE_LIMIT = 102560  # the largest fixture there was before these (gen_scoring's rule)
+STATE_KEYS = ("cards", "masked", "n_draw", "n_disc", "top_draw", "top_disc", "hand", "player", "phase")
+
+
+def _late_state(g):
+    """What is recorded after every action: boards, pile sizes and both pile tops (99: the pile is empty), hand and turn."""
+    s = snapshot(g)
+    return dict(cards=s["cards"], masked=s["masked"], n_draw=s["n_draw"], n_disc=s["n_disc"],
+                top_draw=int(g.drawpile[-1]) if g.drawpile else 99, top_disc=int(g.discard_pile[-1]) if g.discard_pile else 99,
+                hand=s["hand"], player=s["player"], phase=s["phase"])
+
+
+def _late_game(N, indirect, board):
+    cards, masked, draw, disc, hand, player, phase = board
+    g = SkyjoGame(N, 2.0, indirect)
+    g.players_cards = np.asarray(cards, dtype=np.int8).copy()
+    g.players_masked = np.asarray(masked, dtype=np.int8).copy()
+    g.drawpile = [np.int8(x) for x in draw]
+    g.discard_pile = [np.int8(x) for x in disc]
+    g.hand_card = 15 if hand == 15 else np.int8(hand)
+    force_turn(g, player, "place" if phase else "draw")
+    return g
+
+
+def gen_late_boards():
+    """late_boards_N{n}_{ind,dir}.npz.  A board: the reference deals (set_seed), a family of tests/board_inject.py - plain numpy on the
+    dealt state - makes the board, and it goes into a fresh SkyjoGame the way run_scenario injects.  np.random.seed(np_seed) stands in
+    front of the playout and of every single action (a draw from an empty pile reshuffles on the process-global stream).  Arrays, boards
+    stacked on the first axis: names, init_* (whole piles, padded with 99), np_seed; the playouts back to back, board b being rows
+    step_start[b] : step_start[b + 1] - actions, step_actor, step_obs / step_mask (the acting seat, before the action), step_obs_next /
+    step_mask_next (the next seat), step_over and step_{STATE_KEYS} after it -; end_draw / end_disc (+ end_n_draw / end_n_disc),
+    final_score, num_refunded, num_placed, rewards [boards, len(REWARD_CFGS), N]; the 26 actions from a fresh copy - act_legal
+    [boards, 26] (the mask bit) and, for the legal ones in order, rows act_start[b] : act_start[b + 1] of act_over and act_{STATE_KEYS}."""
+    root = os.path.dirname(HERE)
+    if root not in sys.path:
+        sys.path.append(root)
+    from tests import board_inject as bi
+
+    small = ("obs", "mask", "obs_next", "mask_next", "over", "cards", "masked", "legal", "init_draw", "init_disc", "end_draw", "end_disc")
+    sizes = {}
+    for N, count in LATE_BOARDS.items():
+        for indirect in (True, False):
+            rows = {}
+
+            def put(k, v):
+                rows.setdefault(k, []).append(v)
+
+            step_start, act_start = [0], [0]
+            for b in range(count):
+                recipe, phase = bi.RECIPES[b % len(bi.RECIPES)]
+                seed = 1000 * N + 10 * b + int(indirect)
+                dealer = SkyjoGame(N, 2.0, indirect)
+                dealer.set_seed(seed)
+                s = snapshot(dealer)
+                dealt = dict(cards=s["cards"], masked=s["masked"], draw=s["draw"][:s["n_draw"]], disc=s["disc"][:s["n_disc"]], hand=s["hand"],
+                             player=s["player"], phase=s["phase"])
+                board = bi.recipe_board(recipe, phase, dealt, np.random.default_rng(seed), N)
+                bi.check_board(board, N)
+                put("names", "%02d_%s_%s" % (b, recipe, "place" if board[6] else "draw"))
+                g = _late_game(N, indirect, board)
+                for k, v in snapshot(g).items():
+                    put("init_" + k, v)
+                put("np_seed", seed + 1)
+                np.random.seed(seed + 1)
+                rng = np.random.default_rng(seed + 2)
+                steps = 0
+                while not g.is_terminated:
+                    pid = g.expected_action[0]
+                    obs, mask = g.collect_observation(pid)
+                    obs_n, mask_n = g.collect_observation((pid + 1) % N)
+                    a = int(policy_ra(obs, mask, rng=rng))
+                    put("actions", a), put("step_actor", pid)
+                    put("step_obs", np.asarray(obs, dtype=np.int8)), put("step_mask", np.asarray(mask, dtype=np.int8))
+                    put("step_obs_next", np.asarray(obs_n, dtype=np.int8)), put("step_mask_next", np.asarray(mask_n, dtype=np.int8))
+                    put("step_over", int(bool(g.act(pid, a))))
+                    for k, v in _late_state(g).items():
+                        put("step_" + k, v)
+                    steps += 1
+                    assert steps < 4000
+                step_start.append(step_start[-1] + steps)
+                end = snapshot(g)
+                put("end_draw", end["draw"]), put("end_disc", end["disc"]), put("end_n_draw", end["n_draw"]), put("end_n_disc", end["n_disc"])
+                m = g.get_game_metrics()
+                put("final_score", np.asarray(m["final_score"], dtype=np.float64))
+                put("num_refunded", np.asarray(m["num_refunded"], dtype=np.int32))
+                put("num_placed", np.asarray(m["num_placed"], dtype=np.int32))
+                put("rewards", np.stack([calc_rewards(m["final_score"], m["num_refunded"], mr, rr) for mr, rr in REWARD_CFGS]))
+                # one step of each action from a fresh copy
+                pid = _late_game(N, indirect, board).expected_action[0]
+                _, mask = _late_game(N, indirect, board).collect_observation(pid)
+                legal = np.asarray(mask, dtype=np.int8)
+                put("act_legal", legal)
+                for a in np.flatnonzero(legal):
+                    g = _late_game(N, indirect, board)
+                    np.random.seed(seed + 1)
+                    put("act_over", int(bool(g.act(pid, int(a)))))
+                    for k, v in _late_state(g).items():
+                        put("act_" + k, v)
+                act_start.append(act_start[-1] + int((legal != 0).sum()))
+            out = dict(num_players=N, indirect=int(indirect), score_penalty=2.0, reward_cfgs=np.asarray(REWARD_CFGS, dtype=np.float64),
+                       step_start=np.asarray(step_start, dtype=np.int32), act_start=np.asarray(act_start, dtype=np.int32))
+            for k, v in rows.items():
+                if k == "names":
+                    out[k] = np.asarray(v)
+                elif k in ("final_score", "rewards"):
+                    out[k] = np.asarray(v, dtype=np.float64)
+                else:
+                    out[k] = np.asarray(v, dtype=np.int8 if k.endswith(small) else np.int32)
+            for k in ("act_over",) + tuple("act_" + x for x in STATE_KEYS):  # (a board without a legal action leaves none)
+                out.setdefault(k, np.zeros(0, dtype=np.int32))
+            fname = "late_boards_N%d_%s.npz" % (N, "ind" if indirect else "dir")
+            path = os.path.join(OUT, fname)
+            np.savez_compressed(path, **out)
+            sizes[fname] = os.path.getsize(path)
+            assert sizes[fname] <= LATE_LIMIT, (fname, sizes[fname])
+    return sizes
+
+
 def main():
+    if "--late-boards-only" in sys.argv:
+        print("late_boards bytes", gen_late_boards())
+        return
     if "--scoring-only" in sys.argv:
         print("scoring_order bytes", gen_scoring())
         return
@@ -751,6 +879,7 @@ def main():
     print("global", gen_global())
     print("policy_stats", gen_policy_stats())
     print("scoring_order bytes", gen_scoring())
+    print("late_boards bytes", gen_late_boards())
     sz = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("golden bytes", sz)
 

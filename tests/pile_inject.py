@@ -91,16 +91,19 @@ def inject(family, rng, ora, eng=None, games=None):
             se = eng.get_state(g)
             _same_state(se, so, f"dealt state of game {g}")
             episode = se["episode"]  # (the counter-based reshuffle session is keyed by it)
-        draw, disc = fn(so, rng)
-        ora.set_state(g, so["cards"], so["masked"], draw, disc, so["hand"], so["player"], so["phase"])
+        if getattr(fn, "whole_state", False):  # tests/board_inject.py: the boards, the hand and the turn as well as the piles
+            cards, masked, draw, disc, hand, player, phase = fn(so, rng, ora.num_players)
+        else:
+            (draw, disc), cards, masked, hand, player, phase = fn(so, rng), so["cards"], so["masked"], so["hand"], so["player"], so["phase"]
+        ora.set_state(g, cards, masked, draw, disc, hand, player, phase)
         if eng is not None:
-            eng.set_state(g, so["cards"], so["masked"], draw, disc, so["hand"], so["player"], so["phase"], episode=episode)
+            eng.set_state(g, cards, masked, draw, disc, hand, player, phase, episode=episode)
         out[g] = (len(draw), len(disc))
     return out
 
 
 # ------------------------------------------------------------------------------------------ segments
-def oracle_segment(ora, iters, policy_seed, games, tail=1):
+def oracle_segment(ora, iters, policy_seed, games, tail=1, probe=None):
     """`iters` iterations of the on-device policy's restatement, every record; then `tail` more (episodes end on one iteration parity
     and a segment is even: only then do games stand finished) and what stands: piles of `games`, counters, rewards and scores.  Also,
     not for comparison: `resh` uint64 [iters, B], every game's reshuffles so far after each iteration, `resh_episode` (inside the
@@ -111,6 +114,8 @@ def oracle_segment(ora, iters, policy_seed, games, tail=1):
     for t in range(iters):
         parts.append(ora.rollout(1, policy_seed, record_obs=True))
         resh[t], resh_ep[t] = ora.reshuffles()
+        if probe is not None:
+            probe(t)  # (tests/board_inject.py looks at the oracle's games after every iteration)
         for g in np.flatnonzero(resh[t] != (resh[t - 1] if t else before)):
             sizes.append((t, int(g), int(ora.game(int(g)).n_draw) + 2))  # n cards -> n - 1 on the draw pile, one of them drawn (skyjo.py:135-138, 366)
     act, obs, mask, meta, eplen = (np.concatenate([p[k] for p in parts]) for k in range(5))
@@ -224,19 +229,20 @@ def segment_stats(seg, games):
                 redealt_after_rollback=int(after.any(axis=0).sum()), finished=int(seg["finished"].sum()))
 
 
-def play(ora, family, eng=None, rounds=2, inject_seeds=INJECT_SEEDS, seed=SEED, on_segment=None):
+def play(ora, family, eng=None, rounds=2, inject_seeds=INJECT_SEEDS, seed=SEED, on_segment=None, iters=None, probe=None):
     """seed -> WARMUP iterations (games then stand at different points, banks are partly used, dealing runs are in flight) -> `rounds` x
     [reset of ALL games (it takes a banked episode of every game: the next dealing run has work for all) -> inject `family` into every
     game -> one segment of the family's length].  With an engine every step is compared with the oracle's (assert_same).  Returns one
     dict per round: segment_stats + `injected` ({game: (n_draw, n_disc)}) + `seg` (the oracle's segment) and, with an engine, `eng`."""
-    iters = FAMILIES[family][1]
+    iters = FAMILIES[family][1] if iters is None else iters  # (a family given as a function brings its own length)
+    tag = family if isinstance(family, str) else family.__name__
     games = list(range(ora.num_envs))
     ora.seed(None, seed)
     if eng is not None:
         eng.seed(None, seed)
     warm = oracle_segment(ora, WARMUP, POLICY_SEED, games[:8], tail=0)
     if eng is not None:
-        assert_same(engine_segment(eng, WARMUP, POLICY_SEED, games[:8], tail=0), warm, f"{family}: warm-up")
+        assert_same(engine_segment(eng, WARMUP, POLICY_SEED, games[:8], tail=0), warm, f"{tag}: warm-up")
     out = []
     for r in range(rounds):
         ora.reset()
@@ -247,12 +253,14 @@ def play(ora, family, eng=None, rounds=2, inject_seeds=INJECT_SEEDS, seed=SEED, 
             np.testing.assert_array_equal(o.action_mask, mask, err_msg=f"round {r}: masks after the reset")
             np.testing.assert_array_equal(o.agent, agent, err_msg=f"round {r}: agent after the reset")
         injected = inject(family, np.random.default_rng(inject_seeds[r]), ora, eng, games)
-        seg = oracle_segment(ora, iters, POLICY_SEED, games)
+        if probe is not None:
+            probe(-1)  # (the games as injected)
+        seg = oracle_segment(ora, iters, POLICY_SEED, games, probe=probe)
         st = segment_stats(seg, games)
         st.update(injected=injected, seg=seg)
         if eng is not None:
             st["eng"] = engine_segment(eng, iters, POLICY_SEED, games)
-            assert_same(st["eng"], seg, f"{family}: round {r}")
+            assert_same(st["eng"], seg, f"{tag}: round {r}")
         if on_segment is not None:
             on_segment(r, st)
         out.append(st)

@@ -134,6 +134,83 @@ def test_scenarios():
                 np.testing.assert_array_equal(g.final_rewards(mr, rr), d[p + "rewards"][k])
 
 
+LATE = sorted(glob.glob(os.path.join(GOLDEN, "late_boards_*.npz")))
+LATE_STATE = ("n_draw", "n_disc", "top_draw", "top_disc", "hand", "player", "phase")
+
+
+def _late_init(d, b):
+    nd, ns = int(d["init_n_draw"][b]), int(d["init_n_disc"][b])
+    return (d["init_cards"][b], d["init_masked"][b], d["init_draw"][b][:nd], d["init_disc"][b][:ns], int(d["init_hand"][b]),
+            int(d["init_player"][b]), int(d["init_phase"][b]))
+
+
+def _late_state(g):
+    s = g.snapshot()
+    return dict(cards=s["cards"], masked=s["masked"], n_draw=s["n_draw"], n_disc=s["n_disc"], top_draw=int(s["draw"][-1]) if s["n_draw"] else 99,
+                top_disc=int(s["disc"][-1]) if s["n_disc"] else 99, hand=s["hand"], player=s["player"], phase=s["phase"])
+
+
+def _cmp_late_state(g, d, prefix, t, tag):
+    s = _late_state(g)
+    np.testing.assert_array_equal(s["cards"], d[prefix + "cards"][t], err_msg=f"{tag}: cards")
+    np.testing.assert_array_equal(s["masked"], d[prefix + "masked"][t], err_msg=f"{tag}: masked")
+    assert tuple(s[k] for k in LATE_STATE) == tuple(int(d[prefix + k][t]) for k in LATE_STATE), (tag, s)
+
+
+def test_late_board_files_are_all_there():
+    """Six player counts in both observation modes: a missing or renamed file would only empty a parameter set."""
+    assert [os.path.basename(p) for p in LATE] == sorted("late_boards_N%d_%s.npz" % (n, o) for n in (1, 2, 3, 4, 5, 12) for o in ("ind", "dir"))
+
+
+@pytest.mark.parametrize("path", LATE, ids=[os.path.basename(p)[12:-4] for p in LATE])
+def test_late_boards(path):
+    """Boards that random play never reaches (tests/board_inject.py: several refunded columns, one or two actions from the end, open
+    equal columns that were never collapsed), as the reference played them: its seeded-random legal actions to the episode's end -
+    observation and mask of the acting and of the next seat before every action, the state after it, both piles, scores, metrics and
+    rewards at the end - and one step of each of the 26 actions from a fresh copy: the mask bit and, where legal, the successor."""
+    d = dict(np.load(path))  # (every array once: an NpzFile decompresses at each access)
+    N, ind = int(d["num_players"]), bool(d["indirect"])
+    assert len(d["names"]) >= 20 and len(set(d["names"])) == len(d["names"])
+    for b, name in enumerate(d["names"]):
+        g = so.OracleGame(N, float(d["score_penalty"]), ind)
+        g.set_state(*_late_init(d, b))
+        g.seed_legacy_raw(int(d["np_seed"][b]))
+        for t in range(int(d["step_start"][b]), int(d["step_start"][b + 1])):
+            pid = g.expected_action[0]
+            assert pid == d["step_actor"][t], (name, t)
+            obs, mask = g.collect_observation(pid)
+            np.testing.assert_array_equal(obs, d["step_obs"][t], err_msg=f"{name} obs t={t}")
+            np.testing.assert_array_equal(mask, d["step_mask"][t], err_msg=f"{name} mask t={t}")
+            obs, mask = g.collect_observation((pid + 1) % N)
+            np.testing.assert_array_equal(obs, d["step_obs_next"][t], err_msg=f"{name} next seat's obs t={t}")
+            np.testing.assert_array_equal(mask, d["step_mask_next"][t], err_msg=f"{name} next seat's mask t={t}")
+            assert g.act(pid, int(d["actions"][t])) == d["step_over"][t], (name, t)
+            _cmp_late_state(g, d, "step_", t, f"{name} t={t}")
+        assert g.is_terminated, name
+        s = g.snapshot()
+        np.testing.assert_array_equal(s["draw"], d["end_draw"][b][:int(d["end_n_draw"][b])], err_msg=f"{name}: draw pile at the end")
+        np.testing.assert_array_equal(s["disc"], d["end_disc"][b][:int(d["end_n_disc"][b])], err_msg=f"{name}: discard pile at the end")
+        np.testing.assert_array_equal(g.final_score(), d["final_score"][b], err_msg=str(name))
+        nr, npl = g.metrics()
+        np.testing.assert_array_equal(nr, d["num_refunded"][b], err_msg=str(name))
+        np.testing.assert_array_equal(npl, d["num_placed"][b], err_msg=str(name))
+        for k, (mr, rr) in enumerate(d["reward_cfgs"]):
+            np.testing.assert_array_equal(g.final_rewards(mr, rr), d["rewards"][b][k], err_msg=str(name))
+        k = int(d["act_start"][b])
+        for a in range(26):
+            g = so.OracleGame(N, float(d["score_penalty"]), ind)
+            g.set_state(*_late_init(d, b))
+            g.seed_legacy_raw(int(d["np_seed"][b]))
+            pid = g.expected_action[0]
+            obs, mask = g.collect_observation(pid)
+            assert mask[a] == d["act_legal"][b][a], (name, a)
+            if mask[a]:
+                assert g.act(pid, a) == d["act_over"][k], (name, a)
+                _cmp_late_state(g, d, "act_", k, f"{name} action {a}")
+                k += 1
+        assert k == d["act_start"][b + 1]
+
+
 def test_notebook_score_kat():
     """The single known-answer datum in the reference: notebooks/trainpettingzoo.ipynb:52745-52758."""
     cards = np.array([[-1, 9, 7, -2, 4, 2, 0, 7, 4, 0, 3, 5], [0, 7, 1, 10, 7, 2, 0, 6, 1, -1, -1, 9],
