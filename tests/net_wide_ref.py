@@ -3,7 +3,8 @@ csrc/skyjo_policy.hip), on pools of synthetic records of the same kind: X = ``ne
 of the packed net in float64 from ``mlp_pack_wide_ref.unpack(mlp_pack_wide_ref.pack(...))``, layer 1 over K = 16 KS columns instead of 32.
 A case has net_ref's keys, so ``net_ref.check_forward`` and ``net_ref.forward_figures`` take it; T1 (the project's 1e-4 / 8e-2 against X)
 was measured at 31 inputs and is not asserted on a wide case (t1 is False).  numpy only, nothing from the package.  Not collected: a
-helper; tests/test_net_wide_ref.py shows without a GPU that the checks reject three restated wrong kernels.
+helper; tests/test_net_wide_ref.py shows without a GPU that the checks reject three restated wrong kernels and, wherever a kernel runs a
+padding k-step (KS < MKS: ``kernel_ksteps``, ``SWEEP_OBS``), three restated wrong paddings.
 
 Every byte of a record from obs_dim on is random - the action byte, the pad, the mask, the rest; pool rows 1 - 4 are the all-low,
 all-high and alternating rows."""
@@ -15,10 +16,32 @@ from tests import mlp_pack_ref as pk, mlp_pack_wide_ref as wide, net_ref as ref
 
 POOL = ref.POOL
 WRONG = ("first32", "bias31", "byte_obs")
+# Wrong PADDING k-steps (a kernel compiled for MKS k-steps runs MKS - KS of them against k-step KS - 1's loads, and they must add
+# nothing): "one_again" - the constant 1 enters in every step from KS - 1 on, so b1 is added MKS - KS times more; "unmasked" - the
+# repeated record piece KS - 1 enters with all of its 16 bytes; "next_piece" - a padding step s reads record piece s and lets it in.
+# All three take the kernel's MKS and are the right kernel where KS == MKS.
+PADDING_WRONG = ("one_again", "unmasked", "next_piece")
 # (obs_dim, out_dim) of the GPU forward cases: the direct observation of 2, 4 and 12 players, and 47 - K = 48: the bias column IS byte
 # obs_dim of the record, so a kernel that lets that byte in is seen there through a non-zero weight
 FORWARD_SHAPES = ((43, 26), (67, 26), (67, 1), (163, 26), (47, 26))
 GAME_RANGE = (-2, 15)
+# The widths of the forward sweep: the direct observation of 2 .. 12 players (19 + 12 N) and the edges - 32 (the first wide net), the
+# multiples of 16 (the last k-step holds the bias column and no feature), 16 k - 1 (byte obs_dim of the record is the bias column),
+# both sides of the switch between the two instantiations (79 / 80), 162 and 163 (KS = MKS = 11).
+SWEEP_OBS = tuple(sorted({19 + 12 * n for n in range(2, 13)} | {32, 33, 48, 63, 64, 79, 80, 81, 95, 96, 112, 128, 144, 159, 160, 162}))
+# one width per KS 3 .. 11 with a padding k-step wherever there is one (KS 5 and 11 are the instantiations' own sizes)
+ONE_PER_KS = {3: 43, 4: 55, 5: 67, 6: 91, 7: 103, 8: 115, 9: 139, 10: 151, 11: 163}
+# brink-board model rollouts (tests/test_gpu_net_wide.py): (players, indirect observation); games, iterations, the share of games that
+# must end inside the iterations under a net, and under the oracle's own random policy (tests/test_net_wide_ref.py)
+BRINK_CASES = ((2, False), (5, False), (12, False), (5, True))
+BRINK_GAMES, BRINK_T, BRINK_SEED = 130, 24, 33
+BRINK_SHARE = 0.25
+
+
+def kernel_ksteps(obs_dim):
+    """MKS of the instantiation sk_launch_mlp starts for a wide net (csrc/skyjo_policy.hip): 5 up to KS = 5, else 11."""
+    assert obs_dim > 31
+    return 5 if wide.ksteps(obs_dim) <= 5 else 11
 
 
 def engine_record_bytes(obs_dim):
@@ -38,6 +61,33 @@ def wide_records(record_bytes, obs_dim, rng, pool=POOL, feature_range=(-128, 127
     rows[:, :obs_dim] = feat.view(np.uint8)
     assert np.unique(rows[:, :obs_dim], axis=0).shape[0] == pool, "pool observations repeat"
     return rows
+
+
+def padding_inputs(rows, obs_dim, wrong, mks):
+    """The input columns float64 [n, 16 (mks - KS)] of the padding k-steps KS .. mks - 1 of a wrong kernel (the right one: zeros).  A
+    record piece that lies beyond the record's end enters as zeros."""
+    assert wrong in PADDING_WRONG and mks in (5, 11) and wide.ksteps(obs_dim) <= mks
+    KS = wide.ksteps(obs_dim)
+    n, pieces = rows.shape[0], rows.shape[1] // 16
+    pad = np.zeros((n, mks - KS, 16), dtype=np.float64)
+    for i, s in enumerate(range(KS, mks)):
+        if wrong == "one_again":
+            pad[:, i, 15] = 1.0
+        elif wrong == "unmasked":
+            pad[:, i] = rows[:, 16 * (KS - 1):16 * KS].view(np.int8)
+        elif s < pieces:
+            pad[:, i] = rows[:, 16 * s:16 * s + 16].view(np.int8)
+    return pad.reshape(n, 16 * (mks - KS))
+
+
+def padded_tables(u, obs_dim, mks):
+    """The unpacked tables with layer 1 as a kernel of mks k-steps reads it: k-step KS - 1's columns again for every padding step."""
+    KS = wide.ksteps(obs_dim)
+    out = dict(u)
+    for k in ("w1", "w1l"):
+        if k in u:
+            out[k] = np.concatenate([u[k]] + [u[k][:, 16 * (KS - 1):16 * KS]] * (mks - KS), axis=1)
+    return out
 
 
 def inputs(rows, obs_dim, wrong=None):
@@ -93,10 +143,13 @@ def packed_from(u, xk, precision, out_dim, act32=False):
     return out[:, :out_dim]
 
 
-def packed(params, rows, precision, wrong=None, act32=False):
-    """Q of record rows: float64 [n, out_dim]."""
+def packed(params, rows, precision, wrong=None, act32=False, mks=None):
+    """Q of record rows: float64 [n, out_dim].  A wrong padding (PADDING_WRONG) takes ``mks``, the k-steps the kernel is compiled for."""
     obs_dim, out_dim = np.shape(params[0])[1], np.shape(params[4])[0]
     u = wide.unpack(wide.pack(*params, precision=precision), obs_dim, precision)
+    if wrong in PADDING_WRONG:
+        xk = np.concatenate([inputs(rows, obs_dim), padding_inputs(rows, obs_dim, wrong, mks)], axis=1)
+        return packed_from(padded_tables(u, obs_dim, mks), xk, precision, out_dim, act32)
     return packed_from(u, inputs(rows, obs_dim, wrong), precision, out_dim, act32)
 
 

@@ -48,6 +48,28 @@ def test_unpack_of_pack_is_the_rounded_parameters(shape, precision):
         assert np.array_equal(np.asarray(u[name]).view(np.uint8), np.asarray(narrow[name]).view(np.uint8)), name
 
 
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_round_trip_and_size_at_every_wide_obs_dim(precision):
+    """Every obs_dim 32 .. 163 (the GPU sweep compares FusedNet.export() with pack() at each): the size, the round trip of layer 1 with
+    the bias in column K - 1 and zeros between, and the size grows by one k-step's fragments exactly where obs_dim passes a multiple of 16."""
+    step = 8 * 64 * 16 * (2 if precision == "fp32" else 1)
+    for obs_dim in range(32, wide.MAX_OBS + 1):
+        out_dim = 26 if obs_dim % 2 else 1
+        params = pk.weights_b(obs_dim, out_dim)
+        blob = wide.pack(*params, precision=precision)
+        K = wide.columns(obs_dim)
+        assert K == 16 * (obs_dim // 16 + 1) and blob.size == wide.packed_bytes(obs_dim, precision)
+        assert wide.packed_bytes(obs_dim, precision) - wide.packed_bytes(obs_dim - 1, precision) == (step if obs_dim % 16 == 0 else 0)
+        u = wide.unpack(blob, obs_dim, precision)
+        for name, rounded in (("w1", pk.bf16),) + ((("w1l", pk.bf16_lo),) if precision == "fp32" else ()):
+            assert u[name].shape == (256, K), (obs_dim, name)
+            assert np.array_equal(u[name][:, :obs_dim], rounded(pk.SCALE * params[0])), (obs_dim, name)
+            assert not u[name][:, obs_dim:K - 1].any() and np.array_equal(u[name][:, K - 1], rounded(pk.SCALE * params[1])), (obs_dim, name)
+        narrow = pk.unpack(pk.pack(np.zeros((256, 1), np.float32), np.zeros(256, np.float32), *params[2:], precision=precision), precision)
+        for name in ("w2", "w3", "b2", "b3") + (("w2l", "w3l") if precision == "fp32" else ()):
+            assert np.array_equal(np.asarray(u[name]).view(np.uint8), np.asarray(narrow[name]).view(np.uint8)), (obs_dim, name)
+
+
 def test_pieces_start_where_the_narrow_blob_has_them_at_two_ksteps():
     """obs_dim <= 31 is KS = 2: every piece's size - and so its offset - is the narrow blob's."""
     params = pk.weights_b(31, 26)
