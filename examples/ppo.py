@@ -14,8 +14,8 @@ import torch
 
 from skyjo_rl_amd._lib import TGT_HAS_TARGET
 from skyjo_rl_amd.action_mask_model import FLOAT_MIN, FusedNet
-from skyjo_rl_amd.learner import (STATS, STATS_KL, UPDATE_STATS, KLCoeff, NativeAdam, NativeBranch, NativeUpdate, PPOLossBuffers, PPOLossKLBuffers, ppo_loss,
-                                  ppo_loss_kl)
+from skyjo_rl_amd.learner import (STATS, STATS_KL, UPDATE_STATS, KLCoeff, NativeAdam, NativeBranch, NativeUpdate, PPOLossBuffers, PPOLossKLBuffers, native_branch,
+                                  ppo_loss, ppo_loss_kl)
 from skyjo_rl_amd.rollout import Minibatch, behaviour_logits, compute_targets, epoch_order, minibatches, select_rows
 
 
@@ -219,6 +219,10 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
     this path knows ``ent_coef`` (an entropy bonus) and ``vf_clip`` (RLlib's ``vf_clip_param``), and its statistics gain ``entropy``
     and ``clip_fraction``.  ``native_nets`` (needs ``native_loss``): the two branches' forwards and backwards are
     ``learner.NativeBranch``'s kernels on the float32 parameters - a minibatch step is then a fixed sequence of native launches.
+    ``native_nets="auto"`` builds the branches with ``learner.native_branch``: ``NativeBranch`` up to 31 inputs, ``NativeWideBranch`` for
+    the direct observation's 32 to 163.  ``True`` keeps constructing ``NativeBranch`` and so keeps raising its ``ValueError`` on a
+    wider model before anything changes: the value had that meaning before the wide kernels existed, and callers (and tests) rely on
+    the refusal; with ``native_update=True`` both values are the same, since the C side picks the kernels by the engine's observation.
     ``seats`` (needs ``native_batches``): an iterable of seat numbers - the update runs on the rows in which these seats acted, their
     advantages normalised with their own moments (``rollout.select_rows(buf, seats=...)``): ``model`` is the policy of those seats
     in a buffer that ``arena.collect`` filled.  None: every row, as before.  ``kl`` (needs ``native_loss`` and ``behaviour_net``): a
@@ -235,7 +239,7 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
     coefficient was below 1; both are summed on the device and come with the epoch's read.  None: no clipping, every path and every
     result as without the keyword.  ``shuffle`` ("native" needs ``native_batches``): "torch" - an epoch's order is a ``torch.randperm``
     from a generator seeded with ``seed``; "native" - ``rollout.epoch_order(sel, seed, ep)``, ``ep`` counted from 0 inside the call: one
-    native launch pair per epoch, no generator, no fancy-index allocation.  ``native_update`` (needs ``native_nets``, ``shuffle="native"``
+    native launch pair per epoch, no generator, no fancy-index allocation.  ``native_update`` (needs ``native_nets`` True or "auto", ``shuffle="native"``
     and a ``learner.NativeAdam``): the whole update is ONE native call (``learner.NativeUpdate``, ``skyjo_vec_ppo_update``) that queues the
     launches the loop below would make, in its order - parameters, Adam state, nets and every number of the result carry the bits of
     ``native_update=False`` - and the statistics of all epochs are read once, at the end; a non-zero fault word of the shuffles raises
@@ -244,8 +248,10 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
         raise ValueError('shuffle must be "torch" or "native"')
     if shuffle == "native" and not native_batches:
         raise ValueError('shuffle="native" needs native_batches=True')
+    if native_nets not in (False, True, "auto"):
+        raise ValueError('native_nets must be False, True or "auto"')
     if native_update and not (native_nets and shuffle == "native" and isinstance(optimizer, NativeAdam)):
-        raise ValueError('native_update=True needs native_nets=True, shuffle="native" and a learner.NativeAdam as optimizer')
+        raise ValueError('native_update=True needs native_nets=True or "auto", shuffle="native" and a learner.NativeAdam as optimizer')
     if grad_clip is not None:
         if isinstance(grad_clip, bool) or not isinstance(grad_clip, (int, float)) or not (math.isfinite(grad_clip) and grad_clip > 0):
             raise ValueError("grad_clip must be None or a finite number greater than 0")
@@ -263,7 +269,7 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
         if seats is not None and not native_batches:
             raise ValueError("seats belongs to native_batches=True")
         if native_nets and not native_loss:
-            raise ValueError("native_nets=True needs native_loss=True")
+            raise ValueError('native_nets=True (or "auto") needs native_loss=True')
         if native_loss and not native_batches:
             raise ValueError("native_loss=True needs native_batches=True")
         if not native_loss and (ent_coef != 0.0 or vf_clip is not None):
@@ -303,7 +309,8 @@ def ppo_update(model, buf, optimizer, epochs=2, minibatch=1 << 15, clip=0.3, vf_
     # how its gradients reach the parameters
     if native_nets:
         # the branches' own kernels: every call of a step native, no autograd graph, no ``zero_grad`` (``backward`` overwrites the gradients)
-        policy, value_branch = NativeBranch(model.policy, rows), NativeBranch(model.value, rows)
+        make = native_branch if native_nets == "auto" else NativeBranch  # (True: the class of up to 31 inputs, whatever the model's width)
+        policy, value_branch = make(model.policy, rows), make(model.value, rows)
         forward = lambda obs: (policy.forward(obs), value_branch.forward(obs))
 
         def backward(logits, value, res):

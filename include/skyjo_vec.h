@@ -477,9 +477,9 @@ int skyjo_vec_step_collect(skyjo_vec *h, const int32_t *actions, void *records_o
  * The draw of iteration t uses (seed, first_ticket + t) as in skyjo_vec_mlp_act: the same call sequence made one launch at a
  * time from the host gives the same bits.
  * Either observation: the policy net (26 outputs) must live on the engine's device and have the engine's obs_dim, the value net the
- * policy net's obs_dim, precision and device (SKYJO_E_INVALID otherwise).  The learner's native branches (skyjo_vec_mlp_train_*,
- * skyjo_vec_ppo_update) keep 1 <= obs_dim <= 31: a wider model trains through the caller's autograd on the native batches and loss head,
- * with skyjo_vec_mlp_adam_step behind it. */
+ * policy net's obs_dim, precision and device (SKYJO_E_INVALID otherwise).  The learner's native branches serve either observation as well:
+ * skyjo_vec_mlp_train_* at 1 <= obs_dim <= 31, skyjo_vec_mlp_train_wide_* at 32 <= obs_dim <= 163, and skyjo_vec_ppo_update picks the
+ * pair that fits the engine's observation. */
 typedef struct skyjo_vec_rollout_buffers {
   void *records;
   int32_t *actions;
@@ -632,7 +632,7 @@ int skyjo_vec_ppo_loss_kl(const float *logits, const float *log_mask, const floa
                           float *grad_value_out, double *stats_out /* device, 7 */, void *scratch, int64_t scratch_bytes, void *stream);
 
 /* One branch of the model - Linear(obs_dim, 256) - tanh - Linear(256, 256) - tanh - Linear(256, out_dim), 1 <= obs_dim <= 31,
- * 1 <= out_dim <= 32: skyjo_vec_mlp_create's limits - trained on its float32 master parameters, on device: the forward that keeps its
+ * 1 <= out_dim <= 32 (a wider layer 1: skyjo_vec_mlp_train_wide_* below) - trained on its float32 master parameters, on device: the forward that keeps its
  * activations and the backward that reads them, what torch's autograd otherwise does between a minibatch and the loss head and between
  * the loss head and the optimizer.  Needs no handle: the calls run on the current device, on `stream`.  Every product runs on the exact
  * float32 matrix instruction (float32 in, float32 accumulate: an fmaf chain), not on the packed nets' bf16 pairs; tanh is tanhf.
@@ -664,6 +664,29 @@ int skyjo_vec_mlp_train_backward(int32_t obs_dim, int32_t out_dim, const float *
                                  const float *grad_out /* [m][out_dim] */, int64_t m, float *const grads[6] /* overwritten */,
                                  void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The same pair for a branch whose layer 1 is wider: 32 <= obs_dim <= 163 (the direct observation's 19 + 12 num_players features),
+ * 1 <= out_dim <= 32, 1 <= m <= 2^30.  Every width has exactly one implementation: these entries refuse obs_dim <= 31 and >= 164 with
+ * SKYJO_E_INVALID (skyjo_vec_mlp_train_wide_workspace_bytes returns 0), as the pair above refuses obs_dim >= 32.  Parameters,
+ * arguments, validation and everything that is not layer 1 - layers 2 and 3, the row pass of the backward, dW2, dW3, db2, db3, the
+ * finish - are as above, word for word.  What depends on obs_dim:
+ *   the padded width   K = 8 (obs_dim / 8 + 1), integer division: a multiple of the k-group of 8 with at least one free column
+ *                      (32 -> 40, 39 -> 40, 40 -> 48, 43 -> 48, 67 -> 72, 163 -> 168; obs_dim = 31 would give the 32 above).  x is
+ *                      padded with zeros in columns [obs_dim, K - 1) and a 1 in column K - 1, against b1 in W1's column K - 1
+ *   layer 1            one float32 chain over the K padded columns, groups of 8 ascending, within a group k0, k0 + 4, k0 + 1, k0 + 5,
+ *                      k0 + 2, k0 + 6, k0 + 3, k0 + 7: b1 is the chain's LAST term, k = K - 1
+ *   dW1, db1           dW1[j][k] = sum over the rows of dz1[r][j] xpad[r][k] for all K columns, one chain per chunk of 256 rows,
+ *                      rows ascending; column K - 1 of that is db1
+ *   workspace          h1, h2, dz2, dz1 [m][256] each, then one record of 74 016 + 256 K floats per chunk of 256 rows: dW2 [256][256],
+ *                      dW1 [256][K] (columns [obs_dim, K - 1) unused), dW3 [32][256] (rows >= out_dim unused), db2 [256], db3 [32] -
+ *                      4 (4 m 256 + ceil(m / 256) (74 016 + 256 K)) bytes.  At K = 32 the record would be the 82 208 above
+ * The error texts carry these functions' names. */
+int64_t skyjo_vec_mlp_train_wide_workspace_bytes(int32_t obs_dim, int32_t out_dim, int64_t m); /* 0 for invalid arguments */
+int skyjo_vec_mlp_train_wide_forward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, int64_t m,
+                                     float *out /* [m][out_dim] */, void *workspace, int64_t workspace_bytes, void *stream);
+int skyjo_vec_mlp_train_wide_backward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x,
+                                      const float *grad_out /* [m][out_dim] */, int64_t m, float *const grads[6] /* overwritten */,
+                                      void *workspace, int64_t workspace_bytes, void *stream);
+
 /* An epoch's shuffled order of a selection, on device, without a sort: order_out[j] = index[perm(j)], 0 <= j < count, perm a keyed
  * bijection of [0, count) that is a pure function of (count, seed, epoch, j) - one lane per j, no atomics, no cross-lane traffic.  Needs
  * no handle: it runs on the current device, on `stream`.  1 <= count <= 2^30; count == 0 is no work (fault_out is still written);
@@ -686,7 +709,8 @@ int skyjo_vec_rollout_shuffle(const int64_t *index, int64_t count, uint64_t seed
  * (the last slice of an epoch may be short), every slice one learner step - exactly the launches the calls above make when a host loop
  * issues them one by one, in the same order, with the same arguments, on the one stream:
  *   1. skyjo_vec_rollout_gather of the slice (and skyjo_vec_rollout_gather_logits of `behaviour` with the KL term)
- *   2. skyjo_vec_mlp_train_forward of the policy branch, then of the value branch
+ *   2. skyjo_vec_mlp_train_forward of the policy branch, then of the value branch (here and in 4: skyjo_vec_mlp_train_wide_* on an
+ *      engine whose observation has 32 .. 163 features)
  *   3. skyjo_vec_ppo_loss (skyjo_vec_ppo_loss_kl with the KL term)
  *   4. skyjo_vec_mlp_train_backward of the policy branch, then of the value branch
  *   5. skyjo_vec_grad_norm over the twelve gradients - the policy branch's six, then the value branch's - if clipping

@@ -147,6 +147,9 @@ SIGNATURES = {
     "skyjo_vec_mlp_train_workspace_bytes": (I64, [I32, I32, I64]),
     "skyjo_vec_mlp_train_forward": (C.c_int, [I32, I32, VP, VP, I64, VP, VP, I64, VP]),
     "skyjo_vec_mlp_train_backward": (C.c_int, [I32, I32, VP, VP, VP, I64, VP, VP, I64, VP]),
+    "skyjo_vec_mlp_train_wide_workspace_bytes": (I64, [I32, I32, I64]),
+    "skyjo_vec_mlp_train_wide_forward": (C.c_int, [I32, I32, VP, VP, I64, VP, VP, I64, VP]),
+    "skyjo_vec_mlp_train_wide_backward": (C.c_int, [I32, I32, VP, VP, VP, I64, VP, VP, I64, VP]),
     "skyjo_vec_rollout_shuffle": (C.c_int, [VP, I64, U64, U32, VP, VP, VP]),
     "skyjo_vec_ppo_update_workspace_bytes": (I64, [VP, I64, I64, I32]),
     "skyjo_vec_ppo_update": (C.c_int, [VP, C.POINTER(PPOUpdateArgs), VP, I64, VP, VP, VP]),

@@ -1,7 +1,7 @@
 // skyjo_learner.hip - the packed nets' handles and the learner behind the extern "C" boundary of include/skyjo_vec.h: skyjo_vec_mlp_*,
 // skyjo_vec_rollout_targets / _select / _gather / _gather_logits / _shuffle, skyjo_vec_ppo_loss / _kl, skyjo_vec_mlp_train_*, skyjo_vec_grad_norm, skyjo_vec_ppo_update,
 // skyjo_vec_arena_* and skyjo_vec_episode_stats,
-// with their kernels (skyjo_update.h, skyjo_clip.h, skyjo_targets.h, skyjo_batches.h, skyjo_loss.h, skyjo_train.h, skyjo_epoch.h, skyjo_arena.h; what they share: skyjo_learner_util.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
+// with their kernels (skyjo_update.h, skyjo_clip.h, skyjo_targets.h, skyjo_batches.h, skyjo_loss.h, skyjo_train.h, skyjo_train_wide.h, skyjo_epoch.h, skyjo_arena.h; what they share: skyjo_learner_util.h).  A translation unit and a code object of its own: nothing here is part of the environment's sources
 // (skyjo_capi.hip, skyjo_device.h and its parts), and of an engine it sees what skyjo_host.h shows - the record layout, B, G, game_id0,
 // the device and the select scratch.  gfx950 only, no CPU path.
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@
 #include "skyjo_batches.h"
 #include "skyjo_loss.h"
 #include "skyjo_train.h"
+#include "skyjo_train_wide.h"
 #include "skyjo_epoch.h"
 #include "skyjo_arena.h"
 
@@ -506,24 +507,35 @@ int skyjo_vec_ppo_loss_kl(const float *logits, const float *log_mask, const floa
                         scratch_bytes, stream);
 }
 
-// ---- a branch's training forward and backward on its float32 parameters (include/skyjo_vec.h: skyjo_vec_mlp_train_*; skyjo_train.h) ----
+// ---- a branch's training forward and backward on its float32 parameters (include/skyjo_vec.h: skyjo_vec_mlp_train_* for 1 .. 31
+// inputs, skyjo_train.h; skyjo_vec_mlp_train_wide_* for 32 .. 163, skyjo_train_wide.h).  Every width has one implementation: `wide`
+// below says which pair of entries the caller is (or, in skyjo_vec_ppo_update, which the engine's observation needs) ----
 namespace {
 
 constexpr int64_t kTrainMaxRows = (int64_t)1 << 30;
 int64_t train_chunks(int64_t m) { return (m + SKT_CHUNK_ROWS - 1) / SKT_CHUNK_ROWS; }
+bool train_is_wide(int D) { return D > SKT_IN - 1; }
 
 // the checks the two calls share and the workspace's views; 0 or the code fail() returned
-int train_args(const char *who, int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, int64_t m, void *workspace,
-               int64_t workspace_bytes, SkTrainArgs &a) {
+int train_args(const char *who, bool wide, int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, int64_t m,
+               void *workspace, int64_t workspace_bytes, SkTrainArgs &a) {
   const std::string name(who);
   if (!params || !x || !workspace) return fail(SKYJO_E_INVALID, name + ": null argument");
   for (int i = 0; i < 6; i++)
     if (!params[i]) return fail(SKYJO_E_INVALID, name + ": null parameter");
-  if (obs_dim < 1 || obs_dim > SKT_IN - 1 || out_dim < 1 || out_dim > SKT_OUT)
+  if (wide) {
+    if (obs_dim < SKTW_MIN_IN || obs_dim > SKTW_MAX_IN || out_dim < 1 || out_dim > SKT_OUT)
+      return fail(SKYJO_E_INVALID, name + ": obs_dim must be 32..163 and out_dim 1..32");
+  } else if (obs_dim < 1 || obs_dim > SKT_IN - 1 || out_dim < 1 || out_dim > SKT_OUT) {
     return fail(SKYJO_E_INVALID, name + ": obs_dim must be 1..31 and out_dim 1..32");
+  }
   if (m < 1 || m > kTrainMaxRows) return fail(SKYJO_E_INVALID, name + ": m must be at least 1");
-  if (workspace_bytes < skyjo_vec_mlp_train_workspace_bytes(obs_dim, out_dim, m))
+  if (wide) {
+    if (workspace_bytes < skyjo_vec_mlp_train_wide_workspace_bytes(obs_dim, out_dim, m))
+      return fail(SKYJO_E_INVALID, name + ": workspace is smaller than skyjo_vec_mlp_train_wide_workspace_bytes");
+  } else if (workspace_bytes < skyjo_vec_mlp_train_workspace_bytes(obs_dim, out_dim, m)) {
     return fail(SKYJO_E_INVALID, name + ": workspace is smaller than skyjo_vec_mlp_train_workspace_bytes");
+  }
   if (!aligned16(params[2]) || !aligned16(params[4]) || !aligned16(workspace))
     return fail(SKYJO_E_INVALID, name + ": w2, w3 and workspace must be 16-byte aligned");
   for (int i = 0; i < 6; i++)
@@ -543,18 +555,24 @@ int64_t skyjo_vec_mlp_train_workspace_bytes(int32_t obs_dim, int32_t out_dim, in
   return (int64_t)sizeof(float) * (4 * m * SKT_H + train_chunks(m) * SKT_PART);
 }
 
+int64_t skyjo_vec_mlp_train_wide_workspace_bytes(int32_t obs_dim, int32_t out_dim, int64_t m) {
+  if (obs_dim < SKTW_MIN_IN || obs_dim > SKTW_MAX_IN || out_dim < 1 || out_dim > SKT_OUT || m < 1 || m > kTrainMaxRows) return 0;
+  return (int64_t)sizeof(float) * (4 * m * SKT_H + train_chunks(m) * sktw_part(sktw_k(obs_dim)));
+}
+
 // the two calls and skyjo_vec_ppo_update: the checks and the kernels' arguments, nothing launched - and the launches
-static int train_forward_check(const char *who, int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, int64_t m, float *out,
+static int train_forward_check(const char *who, bool wide, int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, int64_t m, float *out,
                                void *workspace, int64_t workspace_bytes, SkTrainArgs &a) {
   if (!out) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
-  if (int rc = train_args(who, obs_dim, out_dim, params, x, m, workspace, workspace_bytes, a)) return rc;
+  if (int rc = train_args(who, wide, obs_dim, out_dim, params, x, m, workspace, workspace_bytes, a)) return rc;
   if ((uintptr_t)out & 3) return fail(SKYJO_E_INVALID, std::string(who) + ": out is not aligned to its element size");
   a.out = out;
   return SKYJO_OK;
 }
 static int train_forward_launch(const SkTrainArgs &a, hipStream_t s) {
   const unsigned tiles = (unsigned)((a.m + SKT_TILE_ROWS - 1) / SKT_TILE_ROWS);
-  hipLaunchKernelGGL(k_mlp_train_fwd, dim3(tiles), dim3(SKT_THREADS), 0, s, a);
+  if (train_is_wide(a.D)) hipLaunchKernelGGL(k_mlp_train_wide_fwd, dim3(tiles), dim3(SKT_THREADS), 0, s, a);
+  else hipLaunchKernelGGL(k_mlp_train_fwd, dim3(tiles), dim3(SKT_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
   return SKYJO_OK;
 }
@@ -562,16 +580,24 @@ static int train_forward_launch(const SkTrainArgs &a, hipStream_t s) {
 int skyjo_vec_mlp_train_forward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, int64_t m, float *out,
                                 void *workspace, int64_t workspace_bytes, void *stream) {
   SkTrainArgs a{};
-  if (int rc = train_forward_check("skyjo_vec_mlp_train_forward", obs_dim, out_dim, params, x, m, out, workspace, workspace_bytes, a)) return rc;
+  if (int rc = train_forward_check("skyjo_vec_mlp_train_forward", false, obs_dim, out_dim, params, x, m, out, workspace, workspace_bytes, a)) return rc;
   return train_forward_launch(a, (hipStream_t)stream);
 }
 
-static int train_backward_check(const char *who, int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, const float *grad_out,
+int skyjo_vec_mlp_train_wide_forward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, int64_t m, float *out,
+                                     void *workspace, int64_t workspace_bytes, void *stream) {
+  SkTrainArgs a{};
+  if (int rc = train_forward_check("skyjo_vec_mlp_train_wide_forward", true, obs_dim, out_dim, params, x, m, out, workspace, workspace_bytes, a))
+    return rc;
+  return train_forward_launch(a, (hipStream_t)stream);
+}
+
+static int train_backward_check(const char *who, bool wide, int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, const float *grad_out,
                                 int64_t m, float *const grads[6], void *workspace, int64_t workspace_bytes, SkTrainArgs &a) {
   if (!grad_out || !grads) return fail(SKYJO_E_INVALID, std::string(who) + ": null argument");
   for (int i = 0; i < 6; i++)
     if (!grads[i]) return fail(SKYJO_E_INVALID, std::string(who) + ": null gradient");
-  if (int rc = train_args(who, obs_dim, out_dim, params, x, m, workspace, workspace_bytes, a)) return rc;
+  if (int rc = train_args(who, wide, obs_dim, out_dim, params, x, m, workspace, workspace_bytes, a)) return rc;
   if ((uintptr_t)grad_out & 3) return fail(SKYJO_E_INVALID, std::string(who) + ": grad_out is not aligned to its element size");
   for (int i = 0; i < 6; i++) {
     if ((uintptr_t)grads[i] & 3) return fail(SKYJO_E_INVALID, std::string(who) + ": a gradient is not aligned to its element size");
@@ -584,6 +610,13 @@ static int train_backward_launch(const SkTrainArgs &a, hipStream_t s) {
   const unsigned tiles = (unsigned)((a.m + SKT_TILE_ROWS - 1) / SKT_TILE_ROWS);
   hipLaunchKernelGGL(k_mlp_train_bwd_rows, dim3(tiles), dim3(SKT_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
+  if (train_is_wide(a.D)) {  // (the row pass reads neither x nor W1: it is the narrow nets')
+    hipLaunchKernelGGL(k_mlp_train_wide_bwd_weights, dim3((unsigned)a.chunks, SKT_SLICES), dim3(SKT_THREADS), 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_mlp_train_wide_bwd_finish, dim3((sktw_part(sktw_k(a.D)) + SKT_THREADS - 1) / SKT_THREADS), dim3(SKT_THREADS), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return SKYJO_OK;
+  }
   hipLaunchKernelGGL(k_mlp_train_bwd_weights, dim3((unsigned)a.chunks, SKT_SLICES), dim3(SKT_THREADS), 0, s, a);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_mlp_train_bwd_finish, dim3((SKT_PART + SKT_THREADS - 1) / SKT_THREADS), dim3(SKT_THREADS), 0, s, a);
@@ -594,7 +627,16 @@ static int train_backward_launch(const SkTrainArgs &a, hipStream_t s) {
 int skyjo_vec_mlp_train_backward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, const float *grad_out,
                                  int64_t m, float *const grads[6], void *workspace, int64_t workspace_bytes, void *stream) {
   SkTrainArgs a{};
-  if (int rc = train_backward_check("skyjo_vec_mlp_train_backward", obs_dim, out_dim, params, x, grad_out, m, grads, workspace, workspace_bytes, a))
+  if (int rc = train_backward_check("skyjo_vec_mlp_train_backward", false, obs_dim, out_dim, params, x, grad_out, m, grads, workspace, workspace_bytes, a))
+    return rc;
+  return train_backward_launch(a, (hipStream_t)stream);
+}
+
+int skyjo_vec_mlp_train_wide_backward(int32_t obs_dim, int32_t out_dim, const float *const params[6], const float *x, const float *grad_out,
+                                      int64_t m, float *const grads[6], void *workspace, int64_t workspace_bytes, void *stream) {
+  SkTrainArgs a{};
+  if (int rc = train_backward_check("skyjo_vec_mlp_train_wide_backward", true, obs_dim, out_dim, params, x, grad_out, m, grads, workspace,
+                                    workspace_bytes, a))
     return rc;
   return train_backward_launch(a, (hipStream_t)stream);
 }
@@ -651,7 +693,7 @@ UpdLayout upd_layout(int D, int64_t count, int64_t minibatch, bool kl) {
   u.logp = take(R * f), u.adv = take(R * f), u.vt = take(R * f), u.val = take(R * f), u.seats = take(R);
   u.old_logits = take(kl ? R * SKYJO_NUM_ACTIONS * f : 0);
   for (int b = 0; b < 2; b++) {
-    u.ws_bytes[b] = skyjo_vec_mlp_train_workspace_bytes(D, kUpdOut[b], R);
+    u.ws_bytes[b] = train_is_wide(D) ? skyjo_vec_mlp_train_wide_workspace_bytes(D, kUpdOut[b], R) : skyjo_vec_mlp_train_workspace_bytes(D, kUpdOut[b], R);
     u.ws[b] = take((size_t)u.ws_bytes[b]), u.out[b] = take(R * kUpdOut[b] * f);
   }
   u.g_logits = take(R * SKYJO_NUM_ACTIONS * f), u.g_value = take(R * f), u.loss_stats = take(SK_LOSS_KL_STATS * sizeof(double));
@@ -758,8 +800,8 @@ int skyjo_vec_ppo_update(skyjo_vec *h, const skyjo_vec_ppo_update_args *a, void 
     UpdSlice &sl = slice[k];
     sl = UpdSlice{};
     for (int b = 0; b < 2; b++) {
-      if (int rc = train_forward_check(who, D, kUpdOut[b], params[b], F(u.obs), m, F(u.out[b]), w + u.ws[b], u.ws_bytes[b], sl.fwd[b])) return rc;
-      if (int rc = train_backward_check(who, D, kUpdOut[b], params[b], F(u.obs), b == 0 ? F(u.g_logits) : F(u.g_value), m, grads[b], w + u.ws[b],
+      if (int rc = train_forward_check(who, train_is_wide(D), D, kUpdOut[b], params[b], F(u.obs), m, F(u.out[b]), w + u.ws[b], u.ws_bytes[b], sl.fwd[b])) return rc;
+      if (int rc = train_backward_check(who, train_is_wide(D), D, kUpdOut[b], params[b], F(u.obs), b == 0 ? F(u.g_logits) : F(u.g_value), m, grads[b], w + u.ws[b],
                                         u.ws_bytes[b], sl.bwd[b]))
         return rc;
     }

@@ -6,7 +6,8 @@ step itself: Adam fused with the re-pack of the updated weights into the ``Fused
 csrc/skyjo_update.h) - the rollout that follows needs no new nets - and with ``max_grad_norm`` RLlib's ``grad_clip`` in front of it: ``grad_norm``
 (``skyjo_vec_grad_norm``, csrc/skyjo_clip.h) takes the global norm of both branches' gradients and the step reads the coefficient from the
 device.  ``NativeBranch`` is what remains in between: one branch's forward, which keeps its activations, and its backward on the float32 master parameters (``skyjo_vec_mlp_train_forward`` / ``_backward``,
-csrc/skyjo_train.h: the exact float32 matrix instruction, no autograd graph, no allocation per step).  ``NativeUpdate`` queues all of it - every epoch and every
+csrc/skyjo_train.h: the exact float32 matrix instruction, no autograd graph, no allocation per step); ``NativeWideBranch`` is the same for the
+direct observation's 32 to 163 inputs (``skyjo_vec_mlp_train_wide_*``, csrc/skyjo_train_wide.h), and ``native_branch`` picks between them.  ``NativeUpdate`` queues all of it - every epoch and every
 minibatch step of an update, the shuffles and the epoch statistics included - behind ONE native call (``skyjo_vec_ppo_update``, csrc/skyjo_epoch.h).
 
 The definition (include/skyjo_vec.h has it in full): the masked softmax of ``action_mask_model.py:58-74`` - logits plus
@@ -352,7 +353,7 @@ UPDATE_STATS = STATS_KL + ("grad_norm", "grad_clipped", "rows")  # the columns o
 
 class NativeUpdate:
     """A whole PPO update behind ONE native call (``skyjo_vec_ppo_update``): ``epochs`` passes over a selection in shuffled slices of
-    ``minibatch`` rows, every slice the step ``examples/ppo.py::ppo_update(native_batches=True, native_loss=True, native_nets=True)``
+    ``minibatch`` rows, every slice the step ``examples/ppo.py::ppo_update(native_batches=True, native_loss=True, native_nets="auto")``
     makes with a ``NativeAdam`` - gather, both branches' forward, the loss head, both backwards, the global-norm clip, Adam with the
     re-pack - queued launch by launch in the same order with the same arguments, so the parameters, the Adam state and both
     ``FusedNet``s end with the same bits; what the host loop does besides (a dozen ctypes calls per step, ``torch.randperm`` and the
@@ -363,7 +364,9 @@ class NativeUpdate:
     schedule; ``kl``: the runs carry the KL term (``buf.behaviour`` and ``kl_coeff``).  The workspace (``workspace``, uint8, of
     ``workspace_bytes``: minibatch columns, activations, the twelve gradients, the order ...), the statistics and the fault word are
     allocated here, once; ``run`` allocates nothing.  The gradients live in the workspace: the parameters' ``.grad`` are NOT touched -
-    neither read nor written nor set."""
+    neither read nor written nor set.  Either observation: there is no width rule here - ``FusedNet.branch_parameters`` accepts 1 to 163
+    inputs and the C side launches the branch kernels that fit the engine's observation (``NativeBranch``'s up to 31 inputs,
+    ``NativeWideBranch``'s from 32)."""
 
     def __init__(self, env, model, policy_net, value_net, optimizer, max_count, minibatch, epochs, kl=False):
         self._L = _lib.load()
@@ -503,7 +506,11 @@ class NativeBranch:
 
     ``seq`` is checked with ``FusedNet.branch_parameters``' rules - three ``nn.Linear`` of shapes [256, D], [256, 256], [O, 256] with
     1 <= D <= 31 and 1 <= O <= 32, contiguous float32 on one GPU - at construction and again at every call (a parameter that was
-    replaced by one of another shape or device is a ``ValueError``, not a launch)."""
+    replaced by one of another shape or device is a ``ValueError``, not a launch).  A wider layer 1 is ``NativeWideBranch``'s;
+    ``native_branch(seq, max_rows)`` returns the class that fits."""
+
+    OBS_RANGE = (1, 31)  # the layer-1 widths of this class's entry points
+    _ENTRIES = ("skyjo_vec_mlp_train_workspace_bytes", "skyjo_vec_mlp_train_forward", "skyjo_vec_mlp_train_backward")
 
     def __init__(self, seq, max_rows):
         self._L = _lib.load()
@@ -515,14 +522,16 @@ class NativeBranch:
             raise ValueError("seq's linears must have two-dimensional weights")
         self.obs_dim, self.out_dim, self.device = int(w1.shape[1]), int(w3.shape[0]), w1.device
         if self.device.type != "cuda":
-            raise ValueError("NativeBranch runs on the GPU: the parameters are on " + str(self.device))
-        if not (1 <= self.obs_dim <= 31 and 1 <= self.out_dim <= 32):
-            raise ValueError("the branch must have 1..31 inputs and 1..32 outputs")
+            raise ValueError(type(self).__name__ + " runs on the GPU: the parameters are on " + str(self.device))
+        lo, hi = self.OBS_RANGE
+        if not (lo <= self.obs_dim <= hi and 1 <= self.out_dim <= 32):
+            raise ValueError(f"the branch must have {lo}..{hi} inputs and 1..32 outputs")
         if max_rows < 1:
             raise ValueError("max_rows must be at least 1")
         self.max_rows = int(max_rows)
         params = self.parameters()
-        nbytes = int(self._L.skyjo_vec_mlp_train_workspace_bytes(self.obs_dim, self.out_dim, self.max_rows))
+        self._workspace_bytes, self._forward, self._backward_entry = (getattr(self._L, n) for n in self._ENTRIES)
+        nbytes = int(self._workspace_bytes(self.obs_dim, self.out_dim, self.max_rows))
         if nbytes <= 0:
             raise ValueError("max_rows is out of range")
         self.workspace = torch.empty((nbytes // 4,), dtype=torch.float32, device=self.device)
@@ -552,9 +561,8 @@ class NativeBranch:
         _column("x", x, torch.float32, (m, self.obs_dim), self.device)
         pp = (C.c_void_p * 6)(*[p.data_ptr() for p in self.parameters()])
         with torch.cuda.device(self.device):
-            _lib.check(self._L.skyjo_vec_mlp_train_forward(self.obs_dim, self.out_dim, pp, x.data_ptr(), m, self.out.data_ptr(),
-                                                           self.workspace.data_ptr(), self.workspace.numel() * 4,
-                                                           torch.cuda.current_stream().cuda_stream))
+            _lib.check(self._forward(self.obs_dim, self.out_dim, pp, x.data_ptr(), m, self.out.data_ptr(), self.workspace.data_ptr(),
+                                     self.workspace.numel() * 4, torch.cuda.current_stream().cuda_stream))
         self._x, self._call = x, self._call + 1
         return self.out[:m]
 
@@ -568,9 +576,8 @@ class NativeBranch:
         params = self.parameters()
         pp = (C.c_void_p * 6)(*[p.data_ptr() for p in params])
         with torch.cuda.device(self.device):
-            _lib.check(self._L.skyjo_vec_mlp_train_backward(self.obs_dim, self.out_dim, pp, self._x.data_ptr(), grad_out.data_ptr(), m,
-                                                            self._gg, self.workspace.data_ptr(), self.workspace.numel() * 4,
-                                                            torch.cuda.current_stream().cuda_stream))
+            _lib.check(self._backward_entry(self.obs_dim, self.out_dim, pp, self._x.data_ptr(), grad_out.data_ptr(), m, self._gg,
+                                            self.workspace.data_ptr(), self.workspace.numel() * 4, torch.cuda.current_stream().cuda_stream))
         return params
 
     @torch.no_grad()
@@ -588,3 +595,24 @@ class NativeBranch:
         ``.grad`` as it does for any function, so a torch-side loss composes with it.  ``x`` gets no gradient.  Backward after another
         ``forward`` of this object raises ``RuntimeError``: the activations are gone."""
         return _BranchFunction.apply(self, x, *self.parameters())
+
+
+class NativeWideBranch(NativeBranch):
+    """``NativeBranch`` for a branch with 32 to 163 inputs - the direct observation's 19 + 12 N features - on the wide entry points
+    (``skyjo_vec_mlp_train_wide_forward`` / ``_backward``, csrc/skyjo_train_wide.h): the same interface, the same guarantees, the same
+    ``ValueError``s before any launch; a branch with fewer than 32 inputs is ``NativeBranch``'s and refused here.  Layer 1 runs over
+    x padded to K = 8 (D // 8 + 1) columns with b1 as the last term of its chain (include/skyjo_vec.h); everything behind layer 1 is
+    ``NativeBranch``'s arithmetic."""
+
+    OBS_RANGE = (32, 163)
+    _ENTRIES = ("skyjo_vec_mlp_train_wide_workspace_bytes", "skyjo_vec_mlp_train_wide_forward", "skyjo_vec_mlp_train_wide_backward")
+
+
+def native_branch(seq, max_rows):
+    """``NativeBranch(seq, max_rows)`` or ``NativeWideBranch(seq, max_rows)``: the class whose entry points serve the width of ``seq``'s
+    first ``nn.Linear`` (up to 31 inputs, and 32 to 163).  Anything else - no such layer, a width of 0 or beyond 163 - goes to
+    ``NativeBranch``, whose checks name what is wrong."""
+    first = next((m for m in seq if isinstance(m, torch.nn.Linear)), None) if hasattr(seq, "__iter__") else None
+    w = getattr(first, "weight", None)
+    wide = isinstance(w, torch.Tensor) and w.dim() == 2 and NativeWideBranch.OBS_RANGE[0] <= w.shape[1] <= NativeWideBranch.OBS_RANGE[1]
+    return (NativeWideBranch if wide else NativeBranch)(seq, max_rows)
