@@ -114,13 +114,18 @@ __device__ __forceinline__ bool consume_spare(const SkParams &P, uint8_t *lp, in
   return true;
 }
 
-// The step kernel's form, in two halves.  `spare_issue` asks for the whole record by LDS-DMA straight into the lane's
-// own (dead: its game is over) slot of the tile - no registers, no LDS writes - and for the two words of bookkeeping;
-// `spare_commit` waits for everything this wavefront has in flight and finishes the hand-over.  Between the two the
-// wavefront steps its live games, which hides the memory round trip of the few lanes that are resetting (about every
-// second iteration has one).  If the bank turns out to be empty the slot holds a stale record: the caller deals in
-// place, which rewrites every word of it.  (Measured and dropped in round 3, EXPERIMENTS.md: the bookkeeping words kept in
-// registers for the whole launch - same time; the record requested a whole iteration earlier, when the game ends - slower.)
+// The step kernel's form, in two halves: a request, and a commit that waits for everything this wavefront has in flight and
+// finishes the hand-over.  Between the two the wavefront steps its live games, which hides the memory round trip of the few
+// lanes that are resetting (about every second iteration has one).  If the bank turns out to be empty the slot holds a stale
+// record: the caller deals in place, which rewrites every word of it.
+// Two forms of the pair.  `spare_issue` / `spare_commit` (steps with caller actions, two players and the generic player counts, and the games
+// beyond the cooperative group below): the resetting lane asks for its whole record by LDS-DMA straight into its own (dead: its
+// game is over) slot of the tile - no registers, no LDS writes, but one instruction per 16-byte piece that occupies all 64 lanes
+// for one or two games.  `spare_issue_coop` / `spare_commit_coop` (the fused rollouts at three and four players): the wavefront
+// fetches the record together, one load and one LDS write (further down).
+// (Measured and dropped in round 3, EXPERIMENTS.md: the bookkeeping words kept in registers for the whole launch - same time; the
+// record requested a whole iteration earlier, when the game ends - slower.  Round 5 #5: a cooperative fetch through loads the
+// COMPILER tracked - slower, for the waits and copies it placed; the cooperative form below keeps its load out of its sight.)
 struct SpareRegs {
   uint32_t dc;
   int head;
@@ -137,6 +142,115 @@ __device__ __forceinline__ void spare_issue(const SkParams &P, uint8_t *lp, uint
 }
 __device__ __forceinline__ bool spare_commit(const SkParams &P, uint8_t *lp, int g, const SpareRegs &r) {
   sk_vm_drain();
+  if (!r.ready) return false;
+  P.spare_ready[(size_t)r.head * (size_t)P.tiles * SK_TILE + g] = 0;  // the dealing run finds the banks that are not full
+  bank_advance(P, lp, g, r.head, r.dc);
+  return true;
+}
+
+// The fused rollouts' form at three and four players (step_body with the on-device policy), cooperative: the record of
+// (slot, game) is CH = `chunks` consecutive 16-byte pieces of the game-major bank, and a resetting game is one lane in about a
+// hundred - so the WAVEFRONT fetches it, GP = 64 / CH = 3 games at a time: lane CH * k + j takes piece j of the k-th resetting
+// game with ONE global_load_dwordx4, and writes it at commit time with ONE ds_write_b128 into that game's column of the tile
+// (lds_tile + j * 1024 + lane_k * 16).  Both functions are entered like the two above - by the resetting lanes only, at the same
+// places - and switch the other lanes on for the few instructions that need them (lanes without a game included: they are fetch
+// lanes, never a source of `head` / `g`).  With fewer than GP resetting games the idle groups fetch and write the FIRST game's
+// pieces once more (same bytes to the same address).  The request leaves the piece and its LDS address in five registers; the
+// commit is the wait, one LDS write and nothing else.  (Measured, EXPERIMENTS.md: switching the idle groups off - a mask
+// computed from the number of games - was 0.7 % slower.)  Resetting games beyond the first GP of an iteration (0.95 % of the
+// lanes reset per iteration: rare) take the LDS-DMA of spare_issue.
+// The load is asm volatile: the compiler neither counts it nor waits for it, and the
+// one wait is the hand-placed vmcnt(0) of the commit - the same wait as spare_commit's (loads and stores share vmcnt and retire
+// in order on this ISA family: nothing weaker is to be had once record stores may be in flight).
+// What it costs: the LDS write of the commit is on the wavefront's path (a game's pieces lie 1 KiB apart, i.e. on the same four
+// banks), where the LDS-DMA landed beside the stepping lanes.  It pays where the step wavefront shares its SIMD's issue slots
+// with a dealing wavefront (65 536 x 3: faster, EXPERIMENTS.md) and loses where it has the SIMD to itself (4 096 x 2, one workgroup of two
+// wavefronts per CU: - 3.6 %, EXPERIMENTS.md) - the two-player kernels, whose BASELINE configuration is that small batch, keep
+// the LDS-DMA.
+// The registers the two statements write with lanes switched on that the surrounding code has switched off.  The compiler's
+// register liveness assumes that a write inside a divergent region touches the region's lanes only, so a temporary DEFINED in
+// there could be given a register that still holds state of the stepping lanes.  Hence sk_coop_reserve(): step_body defines all
+// six under full EXEC at the top of the iteration, in front of `if (valid)`, and the statements take them as read-write ("+v")
+// operands; sk_coop_release() reads d and a under full EXEC again at the end of the iteration.  The registers are then live for ALL
+// lanes in between - also through the stepping lanes' branch, whose lanes hold the pieces while they step (a value that only the
+// commit's branch reads is free for the stepping branch to overwrite: that is how a build without the release lost its pieces).
+// What the compiler still may do is copy such a value under a divergent EXEC (a live-range split, an uncoalesced phi), which would
+// move the owning lanes' part only: tools/check_coop_regs.py compiles the unit and verifies for every instantiation that reserve,
+// request, commit and release name the same registers and that nothing else writes them in between (tests/test_coop_regs.py).
+typedef uint32_t sk_u32x4 __attribute__((ext_vector_type(4)));
+struct CoopRegs {
+  sk_u32x4 d;     // the piece this lane fetches for a resetting game, from the request to the commit
+  uint32_t a, t;  // a: its LDS address (lds_tile + j * 1024 + lane_k * 16); t: the request's scratch
+};
+__device__ __forceinline__ void sk_coop_reserve(CoopRegs &c) { asm volatile("; coop reserve %0 %1 %2" : "=v"(c.d), "=v"(c.a), "=v"(c.t)); }
+__device__ __forceinline__ void sk_coop_release(const CoopRegs &c) { asm volatile("; coop release %0 %1" ::"v"(c.d), "v"(c.a)); }
+// lanes [a, b) as an EXEC mask, its two halves (long long: the immediates print as 32-bit values)
+__device__ __forceinline__ constexpr long long sk_lanes_lo(int a, int b) {
+  return (long long)(((b >= 64 ? ~0ull : (1ull << b) - 1ull) & ~((1ull << a) - 1ull)) & 0xffffffffull);
+}
+__device__ __forceinline__ constexpr long long sk_lanes_hi(int a, int b) {
+  return (long long)(((b >= 64 ? ~0ull : (1ull << b) - 1ull) & ~((1ull << a) - 1ull)) >> 32);
+}
+#define SK_COOP_E0 "s_mov_b32 exec_lo, %[e0l]\n\ts_mov_b32 exec_hi, %[e0h]\n\t"  // lanes [0, 3 CH): all three groups
+#define SK_COOP_E1 "s_mov_b32 exec_lo, %[e1l]\n\ts_mov_b32 exec_hi, %[e1h]\n\t"  // lanes [CH, 3 CH): the second and third
+#define SK_COOP_E2 "s_mov_b32 exec_lo, %[e2l]\n\ts_mov_b32 exec_hi, %[e2h]\n\t"  // lanes [2 CH, 3 CH): the third
+#define SK_COOP_MASKS(CH)                                                                                                   \
+  [ch] "n"(CH), [e0l] "n"(sk_lanes_lo(0, 3 * CH)), [e0h] "n"(sk_lanes_hi(0, 3 * CH)), [e1l] "n"(sk_lanes_lo(CH, 3 * CH)),   \
+      [e1h] "n"(sk_lanes_hi(CH, 3 * CH)), [e2l] "n"(sk_lanes_lo(2 * CH, 3 * CH)), [e2h] "n"(sk_lanes_hi(2 * CH, 3 * CH))
+template <int CH>
+__device__ __forceinline__ void spare_issue_coop(const SkParams &P, uint8_t *lp, uint32_t lds_tile, int lane, int g, SpareRegs &r, CoopRegs &c) {
+  static_assert(64 / CH == 3, "three or four players: three games per group");
+  const size_t G = (size_t)P.tiles * SK_TILE;
+  r.head = LB(H_BANK) % SK_BANK;  // (read before the record is overwritten)
+  r.ready = P.spare_ready[(size_t)r.head * G + g];
+  r.dc = P.deals_consumed[g];
+  const uint32_t voff = (uint32_t)(bank_rec16(P, r.head, g) * 16);
+  // the first three resetting lanes (this code runs under their mask); absent ones = the first: its pieces are fetched and written again
+  unsigned long long m = __builtin_amdgcn_ballot_w64(true);
+  const int l0 = __ffsll((long long)m) - 1;
+  m &= m - 1;
+  const int l1 = m ? __ffsll((long long)m) - 1 : l0;
+  m &= m - 1;
+  const int l2 = m ? __ffsll((long long)m) - 1 : l0;
+  m &= m - 1;
+  const uint32_t s0 = __builtin_amdgcn_readlane(voff, l0), s1 = __builtin_amdgcn_readlane(voff, l1), s2 = __builtin_amdgcn_readlane(voff, l2);
+  // LDS side: group k writes to column l_k - a0 for all, then the steps from one group's column to the next
+  const uint32_t a0 = lds_tile + 16u * (uint32_t)l0, a1 = 16u * (uint32_t)(l1 - l0), a2 = 16u * (uint32_t)(l2 - l1);
+  unsigned long long sv;
+  // t = the lane's piece j = lane - CH * k, a = the k-th game's bank offset + 16 j -> the load; then a = a0 (+ a1 (+ a2)) + 1024 j
+  // (the load stays BEHIND the dozen instructions in front of it: the compiler re-materialises P.spare's SGPR pair with v_readlane_b32, a
+  // vector-memory instruction that reads an SGPR a VALU instruction wrote needs five wait states, and nobody inserts them inside a statement)
+  asm volatile("; coop request %[d] %[a] %[t]\n\ts_mov_b64 %[sv], exec\n\t" SK_COOP_E0
+               "v_mbcnt_lo_u32_b32 %[t], -1, 0\n\tv_mbcnt_hi_u32_b32 %[t], -1, %[t]\n\tv_mov_b32 %[a], %[s0]\n\t"
+               SK_COOP_E1 "v_mov_b32 %[a], %[s1]\n\tv_subrev_u32 %[t], %[ch], %[t]\n\t"
+               SK_COOP_E2 "v_mov_b32 %[a], %[s2]\n\tv_subrev_u32 %[t], %[ch], %[t]\n\t"
+               SK_COOP_E0 "v_lshl_add_u32 %[a], %[t], 4, %[a]\n\tglobal_load_dwordx4 %[d], %[a], %[base]\n\t"
+               "s_nop 0\n\tv_lshl_add_u32 %[a], %[t], 10, %[a0]\n\t"
+               SK_COOP_E1 "v_add_u32 %[a], %[a1], %[a]\n\t"
+               SK_COOP_E2 "v_add_u32 %[a], %[a2], %[a]\n\t"
+               "s_mov_b64 exec, %[sv]"
+               : [d] "+v"(c.d), [t] "+v"(c.t), [a] "+v"(c.a), [sv] "=&s"(sv)
+               : [base] "s"(P.spare), [s0] "s"(s0), [s1] "s"(s1), [s2] "s"(s2), [a0] "s"(a0), [a1] "s"(a1), [a2] "s"(a2), SK_COOP_MASKS(CH)
+               : "memory");
+  if (SK_RARE(m != 0)) {  // (wavefront-uniform) more resetting games than one group serves
+    if ((m >> lane) & 1) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every LDS read of the old record has returned
+      dma_bank_record<false>((const uint8_t *)P.spare, voff, lds_tile, CH);
+    }
+#ifdef SK_DIAG
+    // resets served by the LDS-DMA: word 7 of the tile's section sums, which only -DSK_STAMPS builds use otherwise (skyjo_vec_debug_stamps()[7])
+    if (lane == l0) P.stamps[(size_t)(g / SK_TILE) * 8 + 7] += (unsigned long long)__popcll(m);
+#endif
+  }
+}
+template <int CH>
+__device__ __forceinline__ bool spare_commit_coop(const SkParams &P, uint8_t *lp, int g, const SpareRegs &r, const CoopRegs &c) {
+  unsigned long long sv;
+  // everything this wavefront has in flight (the pieces, the LDS-DMA of the games beyond the group), then the pieces into the tile
+  asm volatile("; coop commit %[d] %[a]\n\ts_waitcnt vmcnt(0)\n\ts_mov_b64 %[sv], exec\n\t" SK_COOP_E0 "ds_write_b128 %[a], %[d]\n\ts_waitcnt lgkmcnt(0)\n\ts_mov_b64 exec, %[sv]"
+               : [sv] "=&s"(sv)
+               : [a] "v"(c.a), [d] "v"(c.d), SK_COOP_MASKS(CH)
+               : "memory");
   if (!r.ready) return false;
   P.spare_ready[(size_t)r.head * (size_t)P.tiles * SK_TILE + g] = 0;  // the dealing run finds the banks that are not full
   bank_advance(P, lp, g, r.head, r.dc);

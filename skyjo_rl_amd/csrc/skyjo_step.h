@@ -142,6 +142,10 @@ __device__ __forceinline__ void step_body(const SkParams &Pin, const int tile, c
   // rollout, -8 % for a step with caller actions) - their LDS is tile | staging (| card chunks of the deferred scoring),
   // nothing else: 25 KB per wavefront for the fused rollout at three players.
   constexpr bool DEFER = POLICY && NP > 0 && NP < 8;
+  // the fused rollouts at three and four players fetch a finished game's next episode cooperatively (skyjo_record.h)
+  constexpr bool COOP = POLICY && NP >= 3 && NP <= 4;
+  constexpr int COOP_CH = COOP ? (H_PILE + SK_NCARDS + 15) / 16 + 2 * NP : 18;  // = P.L.chunks (sk_make_layout)
+  static_assert(PB_BYTES == 32, "COOP_CH: two chunks per player");
   constexpr bool REGACC = NP > 0 && NP < 8;  // (every kernel with a compile-time player count)
   constexpr int NACC = REGACC ? SK_ACC_KINDS * NP : 1;
   double racc_store[NACC];
@@ -187,6 +191,8 @@ __device__ __forceinline__ void step_body(const SkParams &Pin, const int tile, c
       r0 = r1, r1 = r2, r2 = r3, r3 = word;
     }
     int a = -1;
+    CoopRegs coop;
+    if (COOP) sk_coop_reserve(coop);  // (under full EXEC: skyjo_record.h)
     if (valid) {
       const bool over = ((h.w0 >> 16) & F_DONE) != 0;
       if (!POLICY) a = actions[g];
@@ -194,7 +200,10 @@ __device__ __forceinline__ void step_body(const SkParams &Pin, const int tile, c
       const bool acted = !over && !skip;  // this iteration applies (or refuses) an action of this game
       SpareRegs sp;
       const bool resetting = over && P.auto_reset && !skip;
-      if (resetting) spare_issue(P, lp, lds_tile, tile, lane, g, sp);  // lands while the live games step
+      if (resetting) {  // lands while the live games step
+        if (COOP) spare_issue_coop<COOP_CH>(P, lp, lds_tile, lane, g, sp, coop);
+        else spare_issue(P, lp, lds_tile, tile, lane, g, sp);
+      }
       STAMP_T(4);
       if (!over && !skip) {
         const uint32_t v0 = ob.q0, v1 = ob.q1, v2 = ob.q2;  // the acting player's row, read for the previous record
@@ -216,7 +225,7 @@ __device__ __forceinline__ void step_body(const SkParams &Pin, const int tile, c
         a = -1;
         if (P.auto_reset) {
           bool dealt = true;
-          if (!spare_commit(P, lp, g, sp)) {
+          if (!(COOP ? spare_commit_coop<COOP_CH>(P, lp, g, sp, coop) : spare_commit(P, lp, g, sp))) {
             dealt = deal_inline(P, lp, fp, g, tile, lane, sp.head);
             cnt.waits++;  // counts the slow-path deals
           }
@@ -289,6 +298,7 @@ __device__ __forceinline__ void step_body(const SkParams &Pin, const int tile, c
       STAMP(6);
 #endif
     }
+    if (COOP) sk_coop_release(coop);  // (under full EXEC again)
     if (DEFER && ((it & (SK_SCORE_EVERY - 1)) == SK_SCORE_EVERY - 1 || it == iters - 1)) {
       // Scores, rewards and statistics of the games that ended since the last service point (skyjo.py:477-498,
       // skyjo_env.py:293-312), all lanes of the wavefront in one section.  A game cannot end twice in between (an episode
